@@ -19,7 +19,18 @@ centroid normalisation -> nearest-centroid tokens for every frame.  Nothing is c
 the next (the subsample permutation is computed inside every step, on the device).  Inputs are in HBM before
 the timed region starts.  Rank 0 prints ONE JSON line.
 
-Kernel times for the roofline come from HIP events inside the timed steps: the pair the library records around the
+A plain run sets up, runs the W warm-up steps and the K timed steps, writes the last timed step's outputs if
+--dump-outputs DIR is given, and prints the line: `metric`, `value` (frames/s), `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` and the workload.  The timed steps run as the product does, with no timing events of their own.
+Everything below -- the traced step and the roofline, the stage split, `dense_floor` / `verified`, `hard_workload`,
+`cpu_baseline` and `--host-waves` -- runs only under --full.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0's share) as float32 .npy files: centroids.npy
+[k, d], tokens_train.npy / tokens_val.npy (token ids; a fixed seeded sample of at most 2^22 frames each, in frame
+order) and kmeans_objective.npy (the objective of every Lloyd iteration, training by training).  The inputs
+depend on the arguments only, so two builds can be compared output for output.
+
+Under --full, kernel times for the roofline come from HIP events inside the timed steps: the pair the library records around the
 fp16 filter sweep on every exact call, or -- when another kernel class dominates -- a pair around each launch of that
 class.  Which class dominates is decided by one extra UNTIMED step behind the W warm-up steps in which every launch
 is bracketed (`traced_step_ms`, `roofline.kernel_classes`); with W = 0 the timed steps themselves are traced in full.
@@ -55,6 +66,29 @@ CONFIGS = {
     2: dict(name="configs[2]", train=19944, val=2216, n_mels=128, vocab=8192),
     3: dict(name="configs[3] per-GPU shard", train=22500, val=2500, n_mels=64, vocab=8192),
 }
+
+DUMP_TOKENS = 1 << 22      # token ids per dumped set (a seeded sample when there are more)
+DUMP_SEED = 20240601
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir):
+    """Writes the arrays run() returned as float32 .npy files under out_dir (see the module docstring)."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"centroids": res.centroids.float().cpu().numpy()}
+    for name, tok in (("tokens_train", res.tokens_train), ("tokens_val", res.tokens_val)):
+        n = tok.numel()
+        if n > DUMP_TOKENS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_TOKENS))
+            tok = tok[torch.from_numpy(idx).to(tok.device)]
+        ids = tok.cpu().numpy()
+        assert ids.size == 0 or 0 <= ids.min() and ids.max() < (1 << 24), "token ids must be exact in float32"
+        arrays[name] = ids.astype(np.float32)
+    arrays["kmeans_objective"] = np.array([it["obj"] for batch in res.kmeans_stats for it in batch], dtype=np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES, "dumped outputs exceed 64 MB"
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def cpu_logmel_torch(wave, n_mels, hop, n_fft=512, sr=22050):
@@ -113,6 +147,15 @@ def cpu_baseline(n_mels, vocab, L, hop, seed, clips, niter, gpu_note=""):
     }
 
 
+def finish(out, rank, dist):
+    """Rank 0 prints the result line; every rank leaves the process group."""
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -125,14 +168,23 @@ def main():
     ap.add_argument("--vocab", type=int, default=None)
     ap.add_argument("--niter", type=int, default=20)
     ap.add_argument("--clip-seconds", type=float, default=10.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's centroids, tokens and objectives to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the stage split, dense_floor / verified, hard_workload and cpu_baseline "
+                         "(off: the timed steps and the headline line only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dense-floor", action="store_true", help="skip the untimed dense run (dense_floor / verified = null)")
     ap.add_argument("--no-hard-workload", action="store_true", help="skip the noise-dominated workload (hard_workload = null)")
     ap.add_argument("--cpu-clips", type=int, default=256)
     ap.add_argument("--host-waves", action="store_true",
                     help="also time DevicePipeline.run_streaming on pinned host copies of the same waveforms and report it "
-                         "as pcie_inclusive (never `value`)")
+                         "as pcie_inclusive (never `value`); needs --full")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.host_waves and not args.full:
+        ap.error("--host-waves is one of the --full measurements")
     cfg = CONFIGS[args.config]
     n_tr = cfg["train"] if args.train_clips is None else args.train_clips
     n_va = cfg["val"] if args.val_clips is None else args.val_clips
@@ -174,7 +226,8 @@ def main():
     from audio_tokens_amd.synth import synth_clips
 
     be = default_backend(device)
-    be.debug_set("filter_timing", 1)   # the library brackets the stage-1 kernel of its exact calls with HIP events (roofline)
+    if args.full:
+        be.debug_set("filter_timing", 1)   # the library brackets the stage-1 kernel of its exact calls with HIP events (roofline)
     sr, hop, n_fft = 22050, 128, 512
     L = int(round(args.clip_seconds * sr))
     T = be.num_frames(L, hop)
@@ -215,7 +268,7 @@ def main():
         res = pipe.run(wave_tr, wave_va)
         barrier()
         warm_ms.append((time.perf_counter() - t0) * 1e3)
-    if args.warmup > 0:   # one more untimed step, this one traced in full
+    if args.full and args.warmup > 0:   # one more untimed step, this one traced in full
         be.assign_trace, be.assign_trace_only = [], None
         be.filter_stats(reset=True)
         # (the class table wants every kernel's stand-alone duration: this one step keeps the log-mel launches on the main
@@ -234,16 +287,45 @@ def main():
             warm_kinds["pruned"]["kernel_ms"] = w_fms
         warm_step_s = traced_ms * 1e-3
     dom_hint = max(warm_kinds, key=lambda kd: warm_kinds[kd].get("kernel_ms", warm_kinds[kd]["ms"])) if warm_kinds else None
-    be.assign_trace = []
-    be.assign_trace_only = None if dom_hint is None else ({dom_hint} if not (dom_hint == "pruned" and "kernel_ms" in warm_kinds["pruned"]) else set())
-    be.prune_stats(reset=True)
-    be.filter_stats(reset=True)
+    if args.full:
+        be.assign_trace = []
+        be.assign_trace_only = None if dom_hint is None else ({dom_hint} if not (dom_hint == "pruned" and "kernel_ms" in warm_kinds["pruned"]) else set())
+        be.prune_stats(reset=True)
+        be.filter_stats(reset=True)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         res = pipe.run(wave_tr, wave_va)
     barrier()
     elapsed = time.perf_counter() - t0
+    if dist is not None:
+        tmax = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        elapsed = float(tmax.item())
+
+    frames_per_step = (n_tr + n_va) * T * world
+    value = frames_per_step * args.steps / elapsed
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(res, args.dump_outputs)
+    out = {
+        "metric": f"STFT frames/sec through K-means+tokenize, n_mels={n_mels} vocab={vocab}",
+        "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {
+            "workload": (f"{cfg['name']} x{world}: {n_tr}+{n_va} clips/GPU of {args.clip_seconds:g} s @22.05 kHz "
+                         f"({(n_tr + n_va) * T} frames/GPU), n_mels={n_mels}, vocab_size={vocab}, niter={args.niter}, "
+                         f"k-means batches of 10000 files on a {min(256 * vocab, 10000 * T)}-row subsample"),
+            "frames_per_step": frames_per_step, "parallelism": f"dp{world}",
+        },
+        "warmup_step_ms": warm_ms,
+        "comm": comm,
+        "full": args.full,
+    }
+    if not args.full:
+        finish(out, rank, dist)
+        return
+
     trace, be.assign_trace, be.assign_trace_only = (be.assign_trace or []), None, None
     f_rows, f_listed, f_ms, f_sweeps, _, _ = be.filter_stats(timing=True)   # timed steps only
     # One extra, untimed step: the per-stage split, and -- with the counting switch on, which the product leaves off --
@@ -261,14 +343,6 @@ def main():
         dist.all_gather_object(stage_all, {k2: round(v2, 6) for k2, v2 in stage.items()})
     needed, total = be.prune_stats()
     be.debug_set("filter_stats", 0)
-
-    if dist is not None:
-        tmax = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        elapsed = float(tmax.item())
-
-    frames_per_step = (n_tr + n_va) * T * world
-    value = frames_per_step * args.steps / elapsed
 
     # ---- the same step with every acceleration off: the floor, and the check of what was timed -------------
     dense_floor, verified = None, None
@@ -382,17 +456,7 @@ def main():
             **{kd: {"launches": v["launches"], "ms_per_step": v["ms"] / args.steps, "share_of_step_time": step_share(v["ms"])}
                for kd, v in kinds.items() if v["launches"]}}
 
-    out = {
-        "metric": f"STFT frames/sec through K-means+tokenize, n_mels={n_mels} vocab={vocab}",
-        "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {
-            "workload": (f"{cfg['name']} x{world}: {n_tr}+{n_va} clips/GPU of {args.clip_seconds:g} s @22.05 kHz "
-                         f"({(n_tr + n_va) * T} frames/GPU), n_mels={n_mels}, vocab_size={vocab}, niter={args.niter}, "
-                         f"k-means batches of 10000 files on a {min(256 * vocab, 10000 * T)}-row subsample"),
-            "frames_per_step": frames_per_step, "parallelism": f"dp{world}",
-        },
+    out.update({
         "stage_seconds": stage,
         "stage_seconds_note": ("stand-alone cost of each stage, from one extra step with a synchronisation between the stages"
                                + (f"; in the timed steps the log-mel of every k-means batch after the first and of the validation "
@@ -400,14 +464,12 @@ def main():
                                   f"({pipe.beside_clips} clips per launch), so the stages sum to more than ms_per_step"
                                   if pipe.overlaps_logmel(n_tr) else "")),
         "stage_seconds_per_rank": stage_all,
-        "warmup_step_ms": warm_ms,
         "traced_step_ms": traced_ms,
         "verified": verified,
         "dense_floor": dense_floor,
         "hard_workload": None,
         "roofline": roofline,
-        "comm": comm,
-    }
+    })
     if args.host_waves:
         host_tr, host_va = wave_tr.cpu().pin_memory(), wave_va.cpu().pin_memory()
         pipe.run_streaming(host_tr, host_va)                     # warm-up
@@ -451,11 +513,7 @@ def main():
                                                     f"{(n_tr + n_va) * T} frames, i.e. {per_frame:.1f} sweeps per frame")
     else:
         out["cpu_baseline"] = None
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(out, rank, dist)
 
 
 if __name__ == "__main__":

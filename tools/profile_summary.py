@@ -26,7 +26,7 @@ for i, r in enumerate(tr):
         exact.append(dur(r))
 out = os.path.join(root, "profiles", "r01_bench_kernel_stats_top.txt")
 with open(out, "w") as f:
-    f.write("rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline   (MI355X, 1 GPU)\n")
+    f.write("rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline   (MI355X, 1 GPU)\n")
     f.write("5 pipeline runs in the process (1 warm-up + 3 timed + 1 per-stage split); the synthetic-data generation "
             "(at::native kernels) is part of the totals.\n")
     f.write(f"bench line of this run: {d['value']:.4g} frames/s, {d['ms_per_step']:.1f} ms/step\n\n")

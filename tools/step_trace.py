@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel table of ONE pipeline step from a rocprofv3 kernel trace (csv): tools/step_trace.py <kernel_trace.csv> [step]
-The trace is of `bench.py --steps 1 --warmup 1 --no-dense-floor --no-cpu-baseline`: the steps are delimited by the
+The trace is of `bench.py --full --steps 1 --warmup 1 --no-dense-floor --no-cpu-baseline`: the steps are delimited by the
 logmel launches (6 per step).  Prints total time per kernel inside the chosen step and the durations of the
 split_clusters launches in order."""
 import csv
