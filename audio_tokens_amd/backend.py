@@ -793,6 +793,35 @@ class HipBackend(HostHelpers):
     def any_nonfinite(self, v) -> bool:
         return bool(self.nonfinite_flag(v).item())
 
+    def silhouette_samples(self, x, labels, sum_out=None) -> torch.Tensor:
+        """Exact silhouette of every row (at_silhouette_f32: sklearn's float32 recipe in fp64): x [n, d] rows (made
+        float32), labels [n] integers of any values -> device float32 [n] in row order.  sum_out (device float64 [1]),
+        if given, receives the fp64 sum of the result.  Raises ValueError, in sklearn's words, for non-finite rows and
+        for a label count outside 2 .. n - 1."""
+        x = self._f32(x)
+        if x.dim() != 2:
+            raise ValueError(f"Expected 2D array, got {x.dim()}D array instead")
+        if isinstance(labels, np.ndarray):
+            labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64))
+        labels = labels.to(self.device, dtype=torch.int64).reshape(-1).contiguous()
+        n, d = x.shape
+        if labels.numel() != n:
+            raise ValueError(f"Found input variables with inconsistent numbers of samples: [{n}, {labels.numel()}]")
+        if n < 1 or d < 1:
+            raise ValueError(f"Found array with {n} sample(s) and {d} feature(s) while a minimum of 1 is required")
+        if self.any_nonfinite(x):
+            raise ValueError("Input X contains NaN or infinity.")
+        s = self.empty((n,))
+        total = sum_out if sum_out is not None else self.empty((1,), torch.float64)
+        n_labels = self.empty((1,), torch.int64)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_silhouette_f32(self.ctx.handle, _ptr(x), d, _ptr(labels), n, _ptr(s), _ptr(total),
+                                                  _ptr(n_labels), self._stream()))
+        k = int(n_labels.item())
+        if not 2 <= k <= n - 1:
+            raise ValueError("Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)" % k)
+        return s
+
 
 _default: dict = {}
 

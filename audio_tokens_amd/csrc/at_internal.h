@@ -74,6 +74,7 @@ enum at_ws_slot {
     WS_ROW_FLAG,       // one int: a unit-row pass of at_logmel_f32 met a row whose squared norm is not finite
     WS_LOGMEL_MINMAX,  // at_logmel_minmax_f32: per clip {min key, max key, NaN flag, pad}
     WS_FILTER_BLKSTATS, // fp16-split filter: one statistics record per workgroup of a sweep (switch filter_stats)
+    WS_SILHOUETTE,     // at_silhouette_f32: sorted labels, permutation, segments, offsets, norms, rocprim temp storage
     WS_NSLOTS
 };
 
@@ -160,6 +161,9 @@ struct at_ctx {
     hipEvent_t sum_ev;        // behind the last at_sum_f32 launch (its partials and counter are per context)
     hipStream_t sum_stream;
     int sum_used;
+    hipEvent_t sil_ev;        // behind the last at_silhouette_f32 (its scratch, WS_SILHOUETTE, is per context)
+    hipStream_t sil_stream;
+    int sil_used;
 };
 
 // makes launches of `func` with `bytes` of dynamic LDS legal on the context's device (at most one runtime call per

@@ -182,6 +182,7 @@ void at_destroy(at_ctx* ctx) {
     if (ctx->background_stream) (void)AT_HIP_TOLERATE(hipStreamDestroy(ctx->background_stream));
     if (ctx->mt_ready) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->mt_ready));
     if (ctx->sum_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sum_ev));
+    if (ctx->sil_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sil_ev));
     if (ctx->filter_host_misc) (void)AT_HIP_TOLERATE(hipHostFree(ctx->filter_host_misc));
     std::free(ctx->fb_user_copy);
     std::free(ctx->any_user_copy);

@@ -8,6 +8,8 @@
         (processors/cluster_creator.py:42-56)
     faiss.IndexFlatL2                                     ->  IndexFlatL2
         (processors/spec_tokenizer.py:123-127, 77)
+    sklearn.metrics.silhouette_score                      ->  silhouette_score, silhouette_samples
+        (processors/cluster_creator.py:115-117)
 
 Same constructor arguments, method names, return types and error behaviour as the originals for the
 subset the reference uses.  All arithmetic happens in libaudio_tokens_amd.so (HIP, gfx950); this
@@ -29,7 +31,8 @@ import torch
 
 from .backend import default_backend
 
-__all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "normalize_rows"]
+__all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "normalize_rows", "silhouette_samples",
+           "silhouette_score"]
 
 
 def _is_host(x) -> bool:
@@ -616,3 +619,63 @@ class IndexFlatL2:
             ids, dis = self.assign(x)
             D, I = dis.unsqueeze(1), ids.unsqueeze(1)
         return (be.to_host(D), be.to_host(I)) if host else (D, I)
+
+
+def _check_random_state(seed):
+    """sklearn.utils.check_random_state: None -> numpy's global RandomState, an int -> a new RandomState(seed), a
+    RandomState -> itself."""
+    if seed is None or seed is np.random:
+        return np.random.mtrand._rand
+    if isinstance(seed, (int, np.integer)):
+        return np.random.RandomState(seed)
+    if isinstance(seed, np.random.RandomState):
+        return seed
+    raise ValueError("%r cannot be used to seed a numpy.random.RandomState instance" % seed)
+
+
+def _labels_int64(labels):
+    """Integer labels as they are (only the distinct values matter); any other kind through np.unique, as sklearn's
+    LabelEncoder."""
+    if isinstance(labels, torch.Tensor):
+        if labels.dtype.is_floating_point or labels.dtype.is_complex:
+            labels = labels.cpu().numpy()
+        else:
+            return labels.reshape(-1).to(torch.int64)
+    labels = np.asarray(labels).reshape(-1)
+    if labels.dtype.kind not in "iub":
+        labels = np.unique(labels, return_inverse=True)[1].reshape(-1)
+    return torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64))
+
+
+def silhouette_samples(X, labels, backend=None):
+    """sklearn.metrics.silhouette_samples(X, labels) (euclidean) on the device: numpy float32 [n], exact.
+
+    X: numpy array or torch tensor [n, d], on the host or the device; other float dtypes are converted to float32 first
+    and the result is sklearn's float32 computation on those rows.  labels: [n] of any values.  The recipe and its
+    rounding points are at_silhouette_f32's (include/audio_tokens_amd.h)."""
+    be = backend or default_backend()
+    return be.to_host(be.silhouette_samples(X, _labels_int64(labels)))
+
+
+def silhouette_score(X, labels, *, sample_size=None, random_state=None, backend=None):
+    """sklearn.metrics.silhouette_score(X, labels, sample_size=..., random_state=...) (euclidean) on the device: the
+    mean silhouette as a Python float (fp64 sum of the fp32 samples / n).
+
+    The sample is sklearn's own draw, made on the host: check_random_state(random_state).permutation(n)[:sample_size]
+    (None: numpy's global RandomState, which advances exactly as under sklearn); the sampled rows are gathered on the
+    device.  X as for silhouette_samples (other float dtypes become float32)."""
+    be = backend or default_backend()
+    labels = _labels_int64(labels)
+    if sample_size is not None:
+        x = be._f32(X)
+        n = x.shape[0]
+        if labels.numel() != n:
+            raise ValueError(f"Found input variables with inconsistent numbers of samples: [{n}, {labels.numel()}]")
+        if be.any_nonfinite(x):
+            raise ValueError("Input X contains NaN or infinity.")
+        idx = _check_random_state(random_state).permutation(n)[:sample_size]
+        X = be.gather_rows(x, idx.astype(np.int32))
+        labels = labels.to(be.device)[be.from_host(idx.astype(np.int64))]
+    total = be.empty((1,), torch.float64)
+    s = be.silhouette_samples(X, labels, sum_out=total)
+    return float(total.item()) / s.numel()

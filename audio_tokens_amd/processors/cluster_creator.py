@@ -16,7 +16,7 @@ import torch.nn as nn
 from tqdm import tqdm
 
 from ..audio_tokens_config import AudioTokensConfig
-from ..ops import Kmeans, normalize_rows
+from ..ops import Kmeans, normalize_rows, silhouette_score
 from ..utils.prefetch import prefetch
 from ..utils.set_seed import set_seed
 
@@ -125,9 +125,11 @@ class ClusterCreator:
         self.logger.info("Centroids visualization saved")
 
     def evaluate_clustering(self, data, labels):
-        from sklearn.metrics import silhouette_score
+        """The reference's silhouette_score(data, labels, sample_size=10000), exact, on the device
+        (ops.silhouette_score); also returns the score (the reference returns None)."""
         score = silhouette_score(data, labels, sample_size=10000)
         self.logger.info(f"Silhouette Score: {score}")
+        return score
 
 
 if __name__ == "__main__":

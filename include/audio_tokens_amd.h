@@ -327,6 +327,21 @@ int at_token_histogram_i64(at_ctx* ctx, const int64_t* ids, int64_t n, int k, in
 int at_token_stats_f64(at_ctx* ctx, const int64_t* counts, int k, int64_t* sorted_counts,
                        int32_t* sorted_tokens, double* stats, void* stream);
 
+/* Exact silhouette of a labelled sample: sklearn.metrics.silhouette_samples / silhouette_score on float32 rows, the
+ * metric ClusterCreator.evaluate_clustering reports (processors/cluster_creator.py:115-117:
+ * silhouette_score(data, labels, sample_size=10000)).  x: DEVICE [n][d] fp32 rows; labels: DEVICE int64 [n], any
+ * values (only those present count, as after sklearn's LabelEncoder).  sklearn's float32 recipe, in fp64:
+ *   d2 = fl32(((-2 <x_i,x_j>) + |x_i|^2) + |x_j|^2) (dot and norms in fp64), max(d2, 0), 0 for i == j,
+ *   dist = correctly rounded fp32 sqrt;  S[i,c] = fl32(fp64 sum of dist(i,j) over the members j of c, j ascending);
+ *   a = fl32(S[i,own] / (n_own - 1)), b = min over c != own of fl32(S[i,c] / n_c);
+ *   s[i] = fl32(fl32(b - a) / max(a, b)), NaN -> 0 (singleton clusters, a = b = 0).
+ * s: DEVICE fp32 [n] in the caller's row order; *sum (DEVICE double) = fp64 sum of s (score = *sum / n);
+ * *n_labels (DEVICE int64) = number of distinct labels.  sklearn requires 2 <= n_labels <= n - 1: outside that
+ * range s and *sum are computed but meaningless, and checking is the caller's.  Rows must be finite (the caller's
+ * check, as sklearn's check_array).  Deterministic: two calls give the same bits.  n < 2^31. */
+int at_silhouette_f32(at_ctx* ctx, const float* x, int d, const int64_t* labels, int64_t n, float* s,
+                      double* sum, int64_t* n_labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
