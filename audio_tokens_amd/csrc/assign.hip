@@ -1241,9 +1241,11 @@ static int launch_pruned(at_ctx* ctx, const float* x, int64_t n, const float* c,
     const int kp = ng * 32;
     const int ngw = (ng + 31) / 32;
     const size_t img_bytes = sizeof(float) * (size_t)ng * tile_floats(D, 1);
-    const int64_t ntile32 = (n + 31) / 32;
+    // (the long-list redo below runs the pre-pass and the sweep over at least 64 rows, whatever n is)
+    const int64_t n_ws = n < 64 ? 64 : n;
+    const int64_t ntile32 = (n_ws + 31) / 32;
     float* img = static_cast<float*>(at_ws(ctx, WS_CENT_IMG, img_bytes, stream));
-    float* bd = static_cast<float*>(at_ws(ctx, WS_PRUNE_BD, sizeof(float) * (size_t)n, stream));
+    float* bd = static_cast<float*>(at_ws(ctx, WS_PRUNE_BD, sizeof(float) * (size_t)n_ws, stream));
     uint32_t* mask = static_cast<uint32_t*>(at_ws(ctx, WS_PRUNE_MASK, sizeof(uint32_t) * (size_t)ntile32 * ngw, stream));
     if (!img || !bd || !mask) return AT_E_NOMEM;
     // fp32 image (one tile per group, NA = 1: 32 rows, then |c|^2 at [0,32) and indices at [128,160)): built

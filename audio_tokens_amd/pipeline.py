@@ -147,19 +147,34 @@ class DevicePipeline:
         # k-means batches and of the validation clips runs beside the training of the batches before them
         beside = not timing and self.overlaps_logmel(wave_train.shape[0])
         ready = done = None
+        # Host, float64 or strided waves are converted into temporaries on the main stream.  In the overlapped form the
+        # side stream still reads them after _frames_beside has returned, so they are held here until the main stream
+        # has waited for it (below): freed earlier, their blocks would go to the training's own allocations.
+        wave_tr = be._f32(wave_train)
+        wave_va = be._f32(wave_val) if wave_val is not None and wave_val.shape[0] > 0 else None
         if beside:
-            frames_tr, frames_va, T, ready, done, bad = self._frames_beside(
-                be._f32(wave_train), be._f32(wave_val) if wave_val is not None and wave_val.shape[0] > 0 else None, per_rank)
+            frames_tr, frames_va, T, ready, done, bad = self._frames_beside(wave_tr, wave_va, per_rank)
         else:
             if take_flag:
                 be.logmel_nonfinite_take()                 # (whatever earlier log-mel passes of this context left behind)
-            frames_tr, T = self._frames(be._f32(wave_train))
+            frames_tr, T = self._frames(wave_tr)
             # faiss' input check (Clustering::train) on the training frames, from the unit-row pass that wrote them
             bad = be.logmel_nonfinite_take() if take_flag else None
             frames_va = None
-            if wave_val is not None and wave_val.shape[0] > 0:
-                frames_va, _ = self._frames(be._f32(wave_val))
+            if wave_va is not None:
+                frames_va, _ = self._frames(wave_va)
         sync(); secs["logmel"] = time.perf_counter() - t0
+        try:
+            return self._train_and_tokenise(wave_train.shape[0], frames_tr, frames_va, T, ready, done, bad, per_rank, secs, sync)
+        finally:
+            if done is not None:
+                # whatever happened above (an exception included), the main stream waits for the side stream before the
+                # frames and the converted waves it writes and reads can be freed and handed to the main stream again
+                torch.cuda.current_stream(be.device).wait_event(done)
+
+    def _train_and_tokenise(self, n_clips, frames_tr, frames_va, T, ready, done, bad, per_rank, secs, sync):
+        be = self.be
+        take_flag = hasattr(be, "logmel_nonfinite_take")
 
         # k-means: one train() per batch of `clustering_batch_size` files (this rank's share of
         # each batch is clustering_batch_size / world clips), warm-started from the previous batch
@@ -167,7 +182,6 @@ class DevicePipeline:
         km = Kmeans(self.n_mels, self.vocab_size, niter=self.niter, verbose=self.verbose,
                     distributed=self.distributed, process_group=self.process_group, backend=be)
         km.prune = self.prune
-        n_clips = wave_train.shape[0]
         pending = []
         if bad is None:
             if done is not None:
