@@ -375,6 +375,24 @@ class HipBackend(HostHelpers):
             rec.append(("plain", n, d, k, e0, e1))
         return ids, dist
 
+    def knn(self, x, c, k, want_dist=True):
+        """The k nearest centroids of every row (at_knn_f32): x [n, d], c [k_c, d] (made float32, contiguous, on the
+        device) -> (ids [n, k] int64, dist [n, k] float32 or None), ascending (dis, id); slots with nothing to list are
+        (-1, +inf).  Column 0 is assign()'s answer on finite rows.  k < 1 raises RuntimeError."""
+        k = int(k)
+        if k < 1:
+            raise RuntimeError(f"knn: k must be at least 1, got {k}")
+        x, c = self._f32(x), self._f32(c)
+        assert x.dim() == 2 and c.dim() == 2 and x.shape[1] == c.shape[1]
+        n, d = x.shape
+        kc = c.shape[0]
+        ids = self.empty((n, k), torch.int64)
+        dist = self.empty((n, k), torch.float32) if want_dist else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_knn_f32(self.ctx.handle, _ptr(x), n, d, _ptr(c), kc, k, _ptr(ids), _ptr(dist),
+                                           self._stream()))
+        return ids, dist
+
     def assign_hinted(self, x, c, hint_ids, order=None, want_dist=True):
         """Same result as assign(), faster when the hints (the previous assignment) are mostly right.
         hint_ids: int64 [n] per row.  order: what centroid_accum(..., want_order=True) returned for

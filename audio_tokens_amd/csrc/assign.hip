@@ -1140,6 +1140,17 @@ static int launch_anyd(at_ctx* ctx, const float* x, int64_t n, int d, const floa
 
 }  // namespace
 
+size_t at_chunked_image_tile_floats(int d, int na) {
+    return (size_t)tile_rows(na) * DC * ((d + DC - 1) / DC) + CN_PAD;
+}
+
+int at_prep_chunked_image(at_ctx* ctx, const float* c, int k, int d, int na, float* img, hipStream_t stream) {
+    (void)ctx;
+    const int ntiles = (k + tile_rows(na) - 1) / tile_rows(na);
+    AT_LAUNCH(prep_centroids_chunked_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, d, (d + DC - 1) / DC, na, img);
+    return AT_OK;
+}
+
 extern "C" int at_assign_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
                              int64_t* ids, float* dist, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;

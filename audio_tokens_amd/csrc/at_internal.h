@@ -75,6 +75,8 @@ enum at_ws_slot {
     WS_LOGMEL_MINMAX,  // at_logmel_minmax_f32: per clip {min key, max key, NaN flag, pad}
     WS_FILTER_BLKSTATS, // fp16-split filter: one statistics record per workgroup of a sweep (switch filter_stats)
     WS_SILHOUETTE,     // at_silhouette_f32: sorted labels, permutation, segments, offsets, norms, rocprim temp storage
+    WS_KNN_IMG,        // at_knn_f32: chunked centroid image (at_prep_chunked_image)
+    WS_KNN,            // at_knn_f32 general path: keys of a block of rows (in, out), segment offsets, rocprim temp storage
     WS_NSLOTS
 };
 
@@ -164,6 +166,9 @@ struct at_ctx {
     hipEvent_t sil_ev;        // behind the last at_silhouette_f32 (its scratch, WS_SILHOUETTE, is per context)
     hipStream_t sil_stream;
     int sil_used;
+    hipEvent_t knn_ev;        // behind the last at_knn_f32 (WS_KNN_IMG / WS_KNN are per context)
+    hipStream_t knn_stream;
+    int knn_used;
 };
 
 // makes launches of `func` with `bytes` of dynamic LDS legal on the context's device (at most one runtime call per
@@ -290,6 +295,11 @@ int at_filter_redo_rows(at_ctx* ctx, const float* x, int d, const float* c, int 
 int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, int64_t wave_stride, int sample_rate,
                   int n_fft, int hop, int n_mels, const float* fb_user_dev, float* out, int frame_major,
                   hipStream_t stream);
+
+// assign.hip: the centroid image of the any-d sweep (tiles of 32 * na rows, features in chunks of 64, |c|^2 of a tile
+// behind its last chunk, +inf for rows >= k); at_chunked_image_tile_floats(d, na) floats per tile.  Used by knn.hip.
+size_t at_chunked_image_tile_floats(int d, int na);
+int at_prep_chunked_image(at_ctx* ctx, const float* c, int k, int d, int na, float* img, hipStream_t stream);
 
 int at_group_min_dist_f16(at_ctx* ctx, const float* c, int k, int d, const int32_t* cperm, int ng, float* dmin,
                           hipStream_t stream);

@@ -183,6 +183,7 @@ void at_destroy(at_ctx* ctx) {
     if (ctx->mt_ready) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->mt_ready));
     if (ctx->sum_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sum_ev));
     if (ctx->sil_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sil_ev));
+    if (ctx->knn_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->knn_ev));
     if (ctx->filter_host_misc) (void)AT_HIP_TOLERATE(hipHostFree(ctx->filter_host_misc));
     std::free(ctx->fb_user_copy);
     std::free(ctx->any_user_copy);

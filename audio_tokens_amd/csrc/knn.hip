@@ -1,0 +1,445 @@
+// knn.hip -- the k nearest centroids under squared L2 on gfx950 (at_knn_f32, IndexFlatL2.search(x, k)).
+//
+// Arithmetic contract: dis(i,j) is at_assign_f32's value bit for bit (assign.hip, header):
+//   ip, |x|^2, |c|^2 ascending fmaf chains (v_mfma_f32_32x32x2_f32), dis = (xn + cn) - 2*ip in one fma, then the
+//   clamp v < 0 ? 0 : v, which leaves a NaN a NaN; n < 20: the direct form sum (x-c)^2.
+// Listed: the k smallest finite (dis, j) in lexicographic order, ascending; the rest of a row is (-1, +inf).
+//
+// Fused path (2 <= k <= K_FUSED): the dense sweep of assign.hip with its running arg-min replaced by a running
+// per-lane top-KL list (KL = the power of two >= k, at least 4) in registers.  Centroids are staged through LDS by
+// LDS-DMA from the chunked centroid image (assign.hip, at_prep_chunked_image: tiles of 32*NA rows, 64 features per
+// chunk, |c|^2 of the tile behind its last chunk, +inf for pad rows); x rows stay in registers (d = 64, 128: one / two
+// chunks, template specialisations) or are re-read from L2 one chunk per stage (any other d that is a multiple of 4).
+// A finished accumulator gives each lane 16 candidates; the wave first compares their minimum with every lane's
+// KL-th key (one ballot) and then each candidate (one ballot each), so the insert network runs only for candidates
+// that improve some lane.  A lane sees its centroids in ascending index order ((tile, accumulator, register) is
+// ascending in j for a fixed half-wave), so a strict `<` insert that puts a candidate behind its equals keeps the
+// lexicographic (dis, j) order without comparing ids.  The two half-waves (same 32 rows, disjoint centroids) merge
+// once at the end: the elementwise (dis, j)-minimum of one list and the other reversed is a bitonic sequence of the
+// KL smallest, sorted by a bitonic merge network.
+//
+// General path (k > K_FUSED, n < 20, and x without 16-byte rows or d % 4 != 0): blocks of rows x all centroids of
+// keys (dis bits << idbits) | j in the context workspace (same sweep, keys written instead of a list; the direct /
+// scalar-chain form for the other cases), a segmented rocPRIM radix sort per row, and the first k keys decoded.
+// Non-finite distances get the all-ones key and are never listed.
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "at_internal.h"
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int WG = 256;        // 4 waves
+constexpr int DC = 64;         // features per chunk of the centroid image
+constexpr int CN_PAD = 256;    // norms behind the last chunk of a tile (assign.hip)
+constexpr int NA = 4;          // 32-centroid accumulators per tile (128 centroids)
+constexpr int K_FUSED = 32;    // largest k of the fused path
+constexpr int64_t ROWS_PER_LAUNCH = (int64_t)1 << 30;
+constexpr size_t GENERAL_BYTES = (size_t)256 << 20;   // keys (in + out) of one block of the general path
+
+__device__ __forceinline__ void dma_1k(const float* gsrc_lane, float* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc_lane,
+                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+// the orc_assign clamp (a NaN stays a NaN and is never listed)
+__device__ __forceinline__ float clamp0(float v) { return v < 0.0f ? 0.0f : v; }
+
+// sort key of one distance: (bits << idbits) | j; non-finite -> all ones (sorts last, never listed)
+__device__ __forceinline__ uint64_t dis_key(float v, unsigned j, int idbits, uint64_t none) {
+    unsigned b = __float_as_uint(v);
+    if (v == 0.0f) b = 0u;                       // -0 -> +0
+    return b < 0x7f800000u ? (((uint64_t)b << idbits) | j) : none;
+}
+
+// insert (c, id) into the ascending list; entries <= c stay in front of it (the lane's ids ascend)
+template <int KL>
+__device__ __forceinline__ void topk_insert(float (&ld)[KL], unsigned (&li)[KL], float c, unsigned id) {
+#pragma unroll
+    for (int s = KL - 1; s > 0; s--) {
+        const bool lt_prev = c < ld[s - 1], lt_here = c < ld[s];
+        ld[s] = lt_prev ? ld[s - 1] : (lt_here ? c : ld[s]);
+        li[s] = lt_prev ? li[s - 1] : (lt_here ? id : li[s]);
+    }
+    const bool lt0 = c < ld[0];
+    ld[0] = lt0 ? c : ld[0];
+    li[0] = lt0 ? id : li[0];
+}
+
+__device__ __forceinline__ bool lex_less(float da, unsigned ia, float db, unsigned ib) {
+    return da < db || (da == db && ia < ib);
+}
+
+// MODE_TOPK: running top-KL per row, written as [n][k];  MODE_KEYS: every (row, centroid) key, [n][kc]
+enum { MODE_TOPK = 0, MODE_KEYS = 1 };
+
+// NCH > 0: d = 64 * NCH, x in registers; NCH = 0: any d % 4 == 0, x chunk re-read per stage
+template <int NCH, int KL, int MODE, int WPS>
+__global__ void __launch_bounds__(WG, WPS)
+knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const float* __restrict__ img, int ntiles,
+                int kc, int k, long* __restrict__ ids, float* __restrict__ dist, uint64_t* __restrict__ keys,
+                int idbits) {
+    constexpr int R = 32 * NA;
+    constexpr int PIECE_F = R * DC;
+    constexpr int BUF_F = PIECE_F + CN_PAD;
+    extern __shared__ __attribute__((aligned(16))) float smem[];  // 2 * BUF_F floats
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 31;   // x row within the wave's 32 rows == accumulator column
+    const int h = lane >> 5;   // which k of each MFMA k-pair this lane feeds
+    const long row0 = ((long)blockIdx.x * 4 + wave) * 32;
+    const int nch = NCH > 0 ? NCH : nchunks;
+    const size_t tile_f = (size_t)PIECE_F * nch + CN_PAD;
+
+    long r = row0 + j;
+    if (r >= n) r = n - 1;
+    const float* xrow = X + r * (long)(NCH > 0 ? NCH * DC : d);
+    float xn = 0.0f;
+    float xr[NCH > 0 ? NCH : 1][DC / 2];
+    auto load_x = [&](int chx, float (&xv)[DC / 2], int dd) {
+#pragma unroll
+        for (int q = 0; q < DC / 8; q++) {
+            const int f = chx * DC + 8 * q;
+            f32x4 u = {0, 0, 0, 0}, v = {0, 0, 0, 0};
+            if (f < dd) u = *reinterpret_cast<const f32x4*>(xrow + f);
+            if (f + 4 < dd) v = *reinterpret_cast<const f32x4*>(xrow + f + 4);
+            xv[4 * q + 0] = h ? u[1] : u[0];
+            xv[4 * q + 1] = h ? u[3] : u[2];
+            xv[4 * q + 2] = h ? v[1] : v[0];
+            xv[4 * q + 3] = h ? v[3] : v[2];
+        }
+    };
+    if constexpr (NCH > 0) {
+#pragma unroll
+        for (int f = 0; f < NCH * DC; f += 4) {
+            const f32x4 u = *reinterpret_cast<const f32x4*>(xrow + f);
+            xn = __builtin_fmaf(u[0], u[0], xn);
+            xn = __builtin_fmaf(u[1], u[1], xn);
+            xn = __builtin_fmaf(u[2], u[2], xn);
+            xn = __builtin_fmaf(u[3], u[3], xn);
+        }
+#pragma unroll
+        for (int ch = 0; ch < NCH; ch++) load_x(ch, xr[ch], NCH * DC);
+    } else {
+        for (int f = 0; f < d; f += 4) {
+            const f32x4 u = *reinterpret_cast<const f32x4*>(xrow + f);
+            xn = __builtin_fmaf(u[0], u[0], xn);
+            xn = __builtin_fmaf(u[1], u[1], xn);
+            xn = __builtin_fmaf(u[2], u[2], xn);
+            xn = __builtin_fmaf(u[3], u[3], xn);
+        }
+    }
+
+    float ld[KL];
+    unsigned li[KL];
+#pragma unroll
+    for (int s = 0; s < KL; s++) {
+        ld[s] = __builtin_inff();
+        li[s] = 0xffffffffu;
+    }
+    const long krow = row0 + j;                      // this lane's row (for the keys)
+    const uint64_t none = idbits + 31 >= 64 ? ~0ull : ((1ull << (idbits + 31)) - 1ull);
+
+    auto stage_dma = [&](int ct, int ch, float* dst) {
+        const float* src = img + (size_t)ct * tile_f + (size_t)ch * PIECE_F;
+        const int pieces = (ch == nch - 1 ? BUF_F : PIECE_F) / 256;
+        for (int p = wave; p < pieces; p += 4) dma_1k(src + p * 256 + lane * 4, dst + p * 256);
+    };
+    stage_dma(0, 0, smem);
+    __syncthreads();
+
+    const int swz = j & 15;
+    const int nstages = ntiles * nch;
+    f32x16 acc[NA];
+    auto stage = [&](int s, int ct, int ch, const float (&xv)[DC / 2]) {
+        const float* cur = smem + (s & 1) * BUF_F;
+        if (s + 1 < nstages) {
+            const bool wrap = ch + 1 == nch;
+            stage_dma(wrap ? ct + 1 : ct, wrap ? 0 : ch + 1, smem + ((s + 1) & 1) * BUF_F);
+        }
+#pragma unroll
+        for (int a = 0; a < NA; a++) {
+            const float* arow = cur + (a * 32 + j) * DC;
+            f32x16 cacc = acc[a];
+            if (ch == 0) cacc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int q = 0; q < DC / 8; q++) {
+                const int pc = (2 * q + h) ^ swz;
+                const f32x4 av = *reinterpret_cast<const f32x4*>(arow + pc * 4);
+                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], xv[4 * q + 0], cacc, 0, 0, 0);
+                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], xv[4 * q + 1], cacc, 0, 0, 0);
+                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], xv[4 * q + 2], cacc, 0, 0, 0);
+                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], xv[4 * q + 3], cacc, 0, 0, 0);
+            }
+            acc[a] = cacc;
+        }
+        if (ch == nch - 1) {
+#pragma unroll
+            for (int a = 0; a < NA; a++) {
+                // accumulator register rr holds centroid idbase + (rr & 3) + 8 * (rr >> 2)
+                const unsigned idbase = (unsigned)(ct * NA + a) * 32u + 4u * (unsigned)h;
+                float u[16];
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const f32x4 cn = *reinterpret_cast<const f32x4*>(cur + PIECE_F + a * 32 + 8 * g + 4 * h);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) u[4 * g + e] = __builtin_fmaf(-2.0f, acc[a][4 * g + e], xn + cn[e]);
+                }
+                if constexpr (MODE == MODE_KEYS) {
+                    if (krow < n) {
+                        uint64_t* kr = keys + krow * (long)kc;
+#pragma unroll
+                        for (int g = 0; g < 4; g++) {
+                            const unsigned j0 = idbase + 8u * g;
+#pragma unroll
+                            for (int e = 0; e < 4; e++)
+                                if (j0 + e < (unsigned)kc) kr[j0 + e] = dis_key(clamp0(u[4 * g + e]), j0 + e, idbits, none);
+                        }
+                    }
+                } else {
+                    // clamp0(u) < kth only if u < kth (kth >= 0): the minimum decides whether anything can enter
+                    float m = __builtin_fminf(u[0], u[1]);
+#pragma unroll
+                    for (int e = 2; e < 16; e += 2) m = __builtin_fminf(__builtin_fminf(m, u[e]), u[e + 1]);
+                    if (__builtin_amdgcn_ballot_w64(m < ld[KL - 1]) != 0) {
+#pragma unroll
+                        for (int e = 0; e < 16; e++) {
+                            const float cv = clamp0(u[e]);
+                            if (__builtin_amdgcn_ballot_w64(cv < ld[KL - 1]) != 0)
+                                topk_insert<KL>(ld, li, cv, idbase + (unsigned)((e & 3) + 8 * (e >> 2)));
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    };
+
+    if constexpr (NCH > 0) {
+        static_assert(NCH <= 2, "x chunks held in registers: d = 64 or 128");
+        for (int ct = 0; ct < ntiles; ct++) {   // (written out: a chunk index must be a constant here)
+            stage(ct * NCH, ct, 0, xr[0]);
+            if constexpr (NCH == 2) stage(ct * NCH + 1, ct, 1, xr[NCH - 1]);
+        }
+    } else {
+        int ct = 0, ch = 0;
+        for (int s = 0; s < nstages; s++) {
+            load_x(ch, xr[0], d);
+            stage(s, ct, ch, xr[0]);
+            if (++ch == nch) { ch = 0; ct++; }
+        }
+    }
+
+    if constexpr (MODE == MODE_TOPK) {
+        // merge the half-waves: min(A[s], B[KL-1-s]) is bitonic and holds the KL smallest; then sort it
+        float cd[KL];
+        unsigned ci[KL];
+#pragma unroll
+        for (int s = 0; s < KL; s++) {
+            const float od = __shfl_xor(ld[KL - 1 - s], 32);
+            const unsigned oi = (unsigned)__shfl_xor((int)li[KL - 1 - s], 32);
+            const bool take = lex_less(od, oi, ld[s], li[s]);
+            cd[s] = take ? od : ld[s];
+            ci[s] = take ? oi : li[s];
+        }
+#pragma unroll
+        for (int st = KL / 2; st > 0; st /= 2) {
+#pragma unroll
+            for (int s = 0; s < KL; s++) {
+                if (s & st) continue;
+                const bool sw = lex_less(cd[s + st], ci[s + st], cd[s], ci[s]);
+                const float td = cd[s];
+                const unsigned ti = ci[s];
+                cd[s] = sw ? cd[s + st] : cd[s];
+                ci[s] = sw ? ci[s + st] : ci[s];
+                cd[s + st] = sw ? td : cd[s + st];
+                ci[s + st] = sw ? ti : ci[s + st];
+            }
+        }
+        if (h == 0 && krow < n) {
+            long* io = ids + krow * (long)k;
+            float* dout = dist ? dist + krow * (long)k : nullptr;
+#pragma unroll
+            for (int s = 0; s < KL; s++) {
+                if (s < k) {
+                    const bool has = ci[s] != 0xffffffffu;
+                    io[s] = has ? (long)ci[s] : -1L;
+                    if (dout) dout[s] = has ? cd[s] : __builtin_inff();
+                }
+            }
+        }
+    }
+}
+
+// The same keys without the MFMA sweep: n < 20 (faiss's direct form sum (x-c)^2) and rows the sweep cannot read
+// (d % 4 != 0 or not 16-byte aligned: the three ascending scalar chains).  One thread per (row, centroid).
+__global__ void __launch_bounds__(WG)
+knn_keys_scalar_kernel(const float* __restrict__ X, long n, int d, const float* __restrict__ C, int kc, int direct,
+                       uint64_t* __restrict__ keys, int idbits) {
+    const long t = (long)blockIdx.x * WG + threadIdx.x;
+    const long i = t / kc;
+    const int c = (int)(t % kc);
+    if (i >= n) return;
+    const float* xi = X + i * d;
+    const float* cc = C + (size_t)c * d;
+    float v;
+    if (direct) {
+        float acc = 0.0f;
+        for (int f = 0; f < d; f++) {
+            const float df = xi[f] - cc[f];
+            acc = __builtin_fmaf(df, df, acc);
+        }
+        v = acc;
+    } else {
+        float xn = 0.0f, cn = 0.0f, ip = 0.0f;
+        for (int f = 0; f < d; f++) {
+            xn = __builtin_fmaf(xi[f], xi[f], xn);
+            cn = __builtin_fmaf(cc[f], cc[f], cn);
+            ip = __builtin_fmaf(xi[f], cc[f], ip);
+        }
+        v = clamp0(__builtin_fmaf(-2.0f, ip, xn + cn));
+    }
+    const uint64_t none = (1ull << (idbits + 31)) - 1ull;
+    keys[t] = dis_key(v, (unsigned)c, idbits, none);
+}
+
+__global__ void __launch_bounds__(WG) knn_offsets_kernel(unsigned* __restrict__ off, int rows, int kc) {
+    const int t = blockIdx.x * WG + threadIdx.x;
+    if (t <= rows) off[t] = (unsigned)t * (unsigned)kc;
+}
+
+// first k keys of every sorted row -> (ids, dist); past kc or non-finite: (-1, +inf)
+__global__ void __launch_bounds__(WG)
+knn_decode_kernel(const uint64_t* __restrict__ sorted, long rows, int kc, int k, int idbits, long* __restrict__ ids,
+                  float* __restrict__ dist) {
+    const long t = (long)blockIdx.x * WG + threadIdx.x;
+    if (t >= rows * (long)k) return;
+    const long i = t / k;
+    const int p = (int)(t % k);
+    long id = -1;
+    float dv = __builtin_inff();
+    if (p < kc) {
+        const uint64_t key = sorted[i * kc + p];
+        const unsigned b = (unsigned)(key >> idbits);
+        if (b < 0x7f800000u) {
+            id = (long)(key & ((1ull << idbits) - 1ull));
+            dv = __uint_as_float(b);
+        }
+    }
+    ids[t] = id;
+    if (dist) dist[t] = dv;
+}
+
+template <int NCH, int KL, int MODE, int WPS>
+int launch_sweep(at_ctx* ctx, const float* x, int64_t n, int d, const float* img, int ntiles, int kc, int k,
+                 int64_t* ids, float* dist, uint64_t* keys, int idbits, hipStream_t stream) {
+    auto kern = &knn_mfma_kernel<NCH, KL, MODE, WPS>;
+    const size_t lds = 2 * sizeof(float) * (32 * NA * DC + CN_PAD);
+    { const int rc = at_raise_lds(ctx, reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
+    const int nchunks = (d + DC - 1) / DC;
+    for (int64_t r0 = 0; r0 < n; r0 += ROWS_PER_LAUNCH) {
+        const int64_t m = n - r0 < ROWS_PER_LAUNCH ? n - r0 : ROWS_PER_LAUNCH;
+        AT_LAUNCH(kern, dim3((unsigned)((m + 127) / 128)), dim3(WG), lds, stream, x + r0 * d, (long)m, d, nchunks, img,
+                  ntiles, kc, k, ids ? reinterpret_cast<long*>(ids + r0 * k) : nullptr, dist ? dist + r0 * k : nullptr,
+                  keys ? keys + r0 * kc : nullptr, idbits);
+    }
+    return AT_OK;
+}
+
+template <int KL>
+int launch_fused(at_ctx* ctx, const float* x, int64_t n, int d, const float* img, int ntiles, int kc, int k,
+                 int64_t* ids, float* dist, hipStream_t stream) {
+    if (d == 64) return launch_sweep<1, KL, MODE_TOPK, 2>(ctx, x, n, d, img, ntiles, kc, k, ids, dist, nullptr, 0, stream);
+    if (d == 128) return launch_sweep<2, KL, MODE_TOPK, 2>(ctx, x, n, d, img, ntiles, kc, k, ids, dist, nullptr, 0, stream);
+    return launch_sweep<0, KL, MODE_TOPK, 2>(ctx, x, n, d, img, ntiles, kc, k, ids, dist, nullptr, 0, stream);
+}
+
+size_t knn_align(size_t b) { return (b + 255) & ~size_t(255); }
+
+}  // namespace
+
+extern "C" int at_knn_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int kc, int k, int64_t* ids,
+                          float* dist, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    AT_REQUIRE(ctx, "at_knn_f32: ctx is null");
+    AT_REQUIRE(k >= 1, "at_knn_f32: k = %d (k must be at least 1)", k);
+    AT_REQUIRE(n >= 0 && d > 0 && kc > 0 && kc <= (1 << 24), "at_knn_f32: bad sizes n=%lld d=%d k_c=%d", (long long)n,
+               d, kc);
+    if (n == 0) return AT_OK;
+    AT_REQUIRE(x && c && ids, "at_knn_f32: null pointer");
+    AT_HIP(hipSetDevice(ctx->device));
+
+    // The workspace slots are the context's: a call on another stream than the previous one waits for it.
+    if (!ctx->knn_ev) AT_HIP(hipEventCreateWithFlags(&ctx->knn_ev, hipEventDisableTiming));
+    if (ctx->knn_used && ctx->knn_stream != stream) AT_HIP(hipStreamWaitEvent(stream, ctx->knn_ev, 0));
+
+    const bool sweep = n >= 20 && d % 4 == 0 && at_aligned16(x);
+    int rc = AT_OK;
+    int idbits = 1;
+    while ((1 << idbits) < kc) idbits++;
+    const int ntiles = (kc + 32 * NA - 1) / (32 * NA);
+    float* img = nullptr;
+    if (sweep) {
+        img = static_cast<float*>(at_ws(ctx, WS_KNN_IMG, sizeof(float) * ntiles * at_chunked_image_tile_floats(d, NA),
+                                        stream));
+        if (!img) return AT_E_NOMEM;
+        rc = at_prep_chunked_image(ctx, c, kc, d, NA, img, stream);
+        if (rc) return rc;
+    }
+
+    if (sweep && k <= K_FUSED) {
+        if (k <= 4) rc = launch_fused<4>(ctx, x, n, d, img, ntiles, kc, k, ids, dist, stream);
+        else if (k <= 8) rc = launch_fused<8>(ctx, x, n, d, img, ntiles, kc, k, ids, dist, stream);
+        else if (k <= 16) rc = launch_fused<16>(ctx, x, n, d, img, ntiles, kc, k, ids, dist, stream);
+        else rc = launch_fused<32>(ctx, x, n, d, img, ntiles, kc, k, ids, dist, stream);
+    } else {
+        // general path: blocks of rows, every key of a block sorted per row
+        int64_t rows = (int64_t)(GENERAL_BYTES / (2 * sizeof(uint64_t) * (size_t)kc));
+        if (rows < 1) rows = 1;
+        if (rows > n) rows = n;
+        const size_t nkeys = (size_t)rows * kc;
+        size_t sort_bytes = 0;
+        AT_HIP(rocprim::segmented_radix_sort_keys(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                  (unsigned)nkeys, (unsigned)rows, (const unsigned*)nullptr,
+                                                  (const unsigned*)nullptr, 0, (unsigned)(idbits + 31), stream));
+        const size_t b_keys = knn_align(8 * nkeys), b_off = knn_align(4 * (size_t)(rows + 1));
+        unsigned char* w = static_cast<unsigned char*>(at_ws(ctx, WS_KNN, 2 * b_keys + b_off + knn_align(sort_bytes),
+                                                             stream));
+        if (!w) return AT_E_NOMEM;
+        uint64_t* kin = reinterpret_cast<uint64_t*>(w);
+        uint64_t* kout = reinterpret_cast<uint64_t*>(w + b_keys);
+        unsigned* off = reinterpret_cast<unsigned*>(w + 2 * b_keys);
+        void* tmp = w + 2 * b_keys + b_off;
+        AT_LAUNCH(knn_offsets_kernel, dim3((unsigned)((rows + WG) / WG)), dim3(WG), 0, stream, off, (int)rows, kc);
+        for (int64_t r0 = 0; r0 < n && rc == AT_OK; r0 += rows) {
+            const int64_t m = n - r0 < rows ? n - r0 : rows;
+            const float* xb = x + r0 * d;
+            if (sweep) {
+                if (d == 64) rc = launch_sweep<1, 4, MODE_KEYS, 2>(ctx, xb, m, d, img, ntiles, kc, k, nullptr, nullptr, kin, idbits, stream);
+                else if (d == 128) rc = launch_sweep<2, 4, MODE_KEYS, 2>(ctx, xb, m, d, img, ntiles, kc, k, nullptr, nullptr, kin, idbits, stream);
+                else rc = launch_sweep<0, 4, MODE_KEYS, 2>(ctx, xb, m, d, img, ntiles, kc, k, nullptr, nullptr, kin, idbits, stream);
+                if (rc) break;
+            } else {
+                AT_LAUNCH(knn_keys_scalar_kernel, dim3((unsigned)((m * kc + WG - 1) / WG)), dim3(WG), 0, stream, xb,
+                          (long)m, d, c, kc, n < 20 ? 1 : 0, kin, idbits);
+            }
+            size_t sb = sort_bytes;
+            AT_HIP(rocprim::segmented_radix_sort_keys(tmp, sb, (const uint64_t*)kin, kout, (unsigned)(m * kc),
+                                                      (unsigned)m, (const unsigned*)off, (const unsigned*)off + 1, 0,
+                                                      (unsigned)(idbits + 31), stream));
+            AT_LAUNCH(knn_decode_kernel, dim3((unsigned)((m * k + WG - 1) / WG)), dim3(WG), 0, stream, kout, (long)m,
+                      kc, k, idbits, reinterpret_cast<long*>(ids + r0 * k), dist ? dist + r0 * k : nullptr);
+        }
+    }
+    // behind everything this call queued: a later call on another stream waits for it
+    AT_HIP(hipEventRecord(ctx->knn_ev, stream));
+    ctx->knn_stream = stream;
+    ctx->knn_used = 1;
+    return rc;
+}

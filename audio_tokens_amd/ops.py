@@ -555,7 +555,15 @@ def _grouper():
 
 
 class IndexFlatL2:
-    """faiss.IndexFlatL2(d) with add / search(x, 1) / reset / ntotal (spec_tokenizer.py:123-127,77)."""
+    """faiss.IndexFlatL2(d) with add / search(x, k) / reset / ntotal (spec_tokenizer.py:123-127,77).
+
+    search(x, k) returns (D, I), [n, k] float32 / int64, row-major: numpy for host input, device tensors (on the
+    caller's current stream) for device input.  Row i lists the k smallest (dis, j) in lexicographic order, with dis
+    exactly at_assign_f32's value; only centroids with dis < +inf are listed (NaN never is), and the slots left over
+    (k > ntotal, an empty index, NaN rows, rows whose distances all overflow) hold I = -1, D = +inf.  On finite rows
+    column 0 equals search(x, 1) bit for bit.  Deviation from faiss: its heap starts from FLT_MAX rather than +inf, so
+    its empty slots would read D = FLT_MAX.  k >= 2 needs a backend with knn() (else NotImplementedError); k < 1
+    raises RuntimeError, as faiss does."""
 
     def __init__(self, d, backend=None):
         self.d = int(d)
@@ -606,8 +614,10 @@ class IndexFlatL2:
         return be.assign(x, c, want_dist=want_dist)
 
     def search(self, x, k=1):
+        if k < 1:
+            raise RuntimeError(f"IndexFlatL2.search: k must be at least 1, got {k}")
         if k != 1:
-            raise NotImplementedError("IndexFlatL2.search: only k=1 is implemented (the reference's use)")
+            return self._search_k(x, int(k))
         host = _is_host(x)
         be = self.backend
         x = be._f32(x)
@@ -618,6 +628,20 @@ class IndexFlatL2:
         else:
             ids, dis = self.assign(x)
             D, I = dis.unsqueeze(1), ids.unsqueeze(1)
+        return (be.to_host(D), be.to_host(I)) if host else (D, I)
+
+    def _search_k(self, x, k):
+        be = self.backend
+        if not hasattr(be, "knn"):
+            raise NotImplementedError("IndexFlatL2.search: k > 1 needs a backend with knn()")
+        host = _is_host(x)
+        x = be._f32(x)
+        assert x.dim() == 2 and x.shape[1] == self.d, f"expected [n, {self.d}]"
+        if self._c is None:
+            D = torch.full((x.shape[0], k), float("inf"), device=be.device)
+            I = torch.full((x.shape[0], k), -1, dtype=torch.int64, device=be.device)
+        else:
+            I, D = be.knn(x, self._c, k)
         return (be.to_host(D), be.to_host(I)) if host else (D, I)
 
 

@@ -14,6 +14,7 @@
  *       processors/cluster_creator.py:64-66, processors/spec_tokenizer.py:106-109
  *   faiss.IndexFlatL2(d).add(c); .search(x, 1)                             at_assign_f32
  *       processors/spec_tokenizer.py:77, 123-127 (and inside faiss.Kmeans.train)
+ *   faiss.IndexFlatL2(d).search(x, k), k >= 2 (not used by the reference)  at_knn_f32
  *   faiss.Kmeans(d, k, niter).train(x, init_centroids)                     at_rand_perm_mt19937,
  *       processors/cluster_creator.py:42-56                                at_gather_rows_f32,
  *                                                                          at_assign_f32, at_assign_hinted_f32,
@@ -341,6 +342,19 @@ int at_token_stats_f64(at_ctx* ctx, const int64_t* counts, int k, int64_t* sorte
  * check, as sklearn's check_array).  Deterministic: two calls give the same bits.  n < 2^31. */
 int at_silhouette_f32(at_ctx* ctx, const float* x, int d, const int64_t* labels, int64_t n, float* s,
                       double* sum, int64_t* n_labels, void* stream);
+
+/* The k nearest centroids under squared L2 (IndexFlatL2.search(x, k)).  dis(i,j) is at_assign_f32's value bit for bit
+ * (the direct form for n < 20); a centroid is listed only if dis(i,j) < +inf (NaN never is).  Row i of the output holds
+ * the k smallest (dis, j) in lexicographic order, ascending (ties: lower j first); slots with nothing to list hold
+ * id -1 and +inf (k > k_c, NaN rows, rows whose distances all overflow).  So ids[i*k] / dist[i*k] equal
+ * at_assign_f32's answer for every finite row.
+ *   x: [n][d] fp32; c: [k_c][d] fp32, 1 <= k_c <= 2^24; k >= 1 (k < 1: AT_E_INVALID);
+ *   ids: int64 [n][k]; dist_or_null: float [n][k].
+ * 2 <= k <= 32 on 16-byte aligned rows with d % 4 == 0 and n >= 20: one fused sweep with a running top-k per row.
+ * Otherwise blocks of rows x all centroids of sort keys (at most 256 MiB of context workspace) and a segmented radix
+ * sort per row.  A call on another stream than the context's previous at_knn_f32 waits for that call. */
+int at_knn_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k_c, int k, int64_t* ids,
+               float* dist_or_null, void* stream);
 
 #ifdef __cplusplus
 }
