@@ -238,7 +238,9 @@ class HipBackend(HostHelpers):
     # -- operators ---------------------------------------------------------------------------
     def logmel(self, wave, sample_rate=22050, n_fft=512, hop=128, n_mels=64, fb=None,
                frame_major=False, l2norm=False, out=None) -> torch.Tensor:
-        """wave [n_clips, L] (or [L]) -> [n_clips, n_mels, T], or [n_clips*T, n_mels] if frame_major."""
+        """wave [n_clips, L] (or [L]) -> [n_clips, n_mels, T], or [n_clips*T, n_mels] if frame_major.
+        n_fft: any even size from 64 to 4096 (odd sizes raise NativeError: torch counts their frames differently);
+        1 <= hop <= n_fft, L > n_fft/2."""
         wave = self._f32(wave)
         if wave.dim() == 1:
             wave = wave.unsqueeze(0)

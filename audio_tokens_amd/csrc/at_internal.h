@@ -109,6 +109,7 @@ struct at_debug {
     int visit_bits;       // AT_VISIT_BITS       distance bits of the visiting-order key (0..8; default 8)
     int filter_stats;     // AT_FILTER_STATS     1 = the sweeps count accumulators / tiles for at_prune_stats, at_filter_stats
     int accum_buckets;    // AT_ACCUM_BUCKETS    0 = member lists by radix sort (the only form for k > 16 384)
+    int logmel_fallback;  // AT_LOGMEL_FALLBACK  1 = Bluestein form of the log-mel transform for every n_fft that is not a power of two
     int filter_timing;    // AT_FILTER_TIMING    1 = exact calls bracket their stage-1 kernel with two timing events (bench.py; off in the product)
 };
 
@@ -123,7 +124,7 @@ struct at_ctx {
     hipEvent_t mt_ready;   // behind the generation of WS_MT_RAW
     int mt_have;
     uint32_t mt_seed;
-    int any_sr, any_nfft, any_nmels;   // what WS_LOGMEL_ANY holds
+    int any_sr, any_nfft, any_nmels, any_form;   // what WS_LOGMEL_ANY holds (form: 0 power of two, 1 mixed radix, 2 Bluestein)
     float* any_user_copy;
     float* fb_user_copy;   // host copy of the user filterbank the tables were built from (malloc'd; compared per call)
     int n_cus;             // multiProcessorCount of the device (read once in at_create)
@@ -291,7 +292,7 @@ int at_filter_redo_rows(at_ctx* ctx, const float* x, int d, const float* c, int 
                         const uint32_t* aux, int64_t* ids, float* dist, const unsigned* count_dev, unsigned amb_cap,
                         hipStream_t stream);
 
-// logmel_any.hip: every power-of-two n_fft other than 512
+// logmel_any.hip: every even n_fft other than 512
 int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, int64_t wave_stride, int sample_rate,
                   int n_fft, int hop, int n_mels, const float* fb_user_dev, float* out, int frame_major,
                   hipStream_t stream);

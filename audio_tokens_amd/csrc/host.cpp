@@ -70,6 +70,7 @@ const DebugField kDebugFields[] = {
     {"filter_stats", "AT_FILTER_STATS", &at_debug::filter_stats, 0},
     {"visit_bits", "AT_VISIT_BITS", &at_debug::visit_bits, 8},
     {"filter_timing", "AT_FILTER_TIMING", &at_debug::filter_timing, 0},
+    {"logmel_fallback", "AT_LOGMEL_FALLBACK", &at_debug::logmel_fallback, 0},
 };
 }  // namespace
 

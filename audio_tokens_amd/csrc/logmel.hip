@@ -410,8 +410,10 @@ static int logmel_impl(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t 
                        const float* fb_or_null, float* out, int layout, int fuse_l2norm,
                        unsigned* minmax, hipStream_t stream) {
     AT_REQUIRE(ctx, "at_logmel_f32: ctx is null");
-    AT_REQUIRE(n_fft >= 64 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0,
-               "at_logmel_f32: n_fft=%d not supported (a power of two from 64 to 4096)", n_fft);
+    AT_REQUIRE(n_fft >= 64 && n_fft <= 4096, "at_logmel_f32: n_fft=%d out of range (an even size from 64 to 4096)", n_fft);
+    AT_REQUIRE((n_fft & 1) == 0,
+               "at_logmel_f32: odd n_fft=%d is not supported (torch counts 1 + (L - 1) / hop frames for odd sizes, "
+               "at_num_frames has no n_fft argument; use an even size from 64 to 4096)", n_fft);
     AT_REQUIRE(hop >= 1 && hop <= n_fft, "at_logmel_f32: hop=%d out of range [1, %d]", hop, n_fft);
     AT_REQUIRE(n_mels >= 1 && n_mels <= 1024, "at_logmel_f32: n_mels=%d out of range", n_mels);
     AT_REQUIRE(n_clips >= 0 && n_clips <= 65535 * 1024L, "at_logmel_f32: n_clips out of range");

@@ -1,4 +1,4 @@
-// logmel_any.hip -- at_logmel_f32 for every power-of-two n_fft other than 512 (64 .. 4096).
+// logmel_any.hip -- at_logmel_f32 for every even n_fft other than 512 (64 .. 4096).
 //
 // The reference exposes n_fft / hop_length as configuration (audio_tokens_config.py:39-40; its README
 // documents 1024 / 512) and hands them to torchaudio's MelSpectrogram (processors/spectrogram_generator.py:28-33).
@@ -10,14 +10,20 @@
 // memory, twiddle and window tables sit in LDS.  Then the same even/odd untangling to the M + 1 power bins, the banded
 // mel dot products, 10 log10.  Same arithmetic contract as the tuned kernel (fp32 throughout, |X|^2 as re^2 + im^2,
 // clamp at 1e-10), same tolerance against the CPU restatement (tests/test_gpu_ops.py::test_logmel_other_nfft).
+// The even sizes that are not powers of two (400, 480, 1000, ...) take logmel_mixed_kernel further down: run-time
+// radices from {8, 4, 2, 3, 5, 7} where M has no larger prime factor, Bluestein's chirp transform elsewhere
+// (logmel_mixed_core.h; tests/test_gpu_logmel_nfft.py).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "at_internal.h"
+#include "logmel_mixed_core.h"
 
 namespace {
+
+using namespace lmx;
 
 constexpr int WG = 256;
 
@@ -36,49 +42,6 @@ struct AnyParams {
     float* out;
     int frame_major;
 };
-
-struct cx {
-    float re, im;
-};
-__device__ __forceinline__ cx cadd(cx a, cx b) { return {a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ cx csub(cx a, cx b) { return {a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ cx cmul(cx a, cx w) {
-    return {__builtin_fmaf(a.re, w.re, -(a.im * w.im)), __builtin_fmaf(a.re, w.im, a.im * w.re)};
-}
-// forward DFTs in registers, natural order in and out
-__device__ __forceinline__ void dft2(cx (&v)[2]) {
-    const cx a = v[0], b = v[1];
-    v[0] = cadd(a, b);
-    v[1] = csub(a, b);
-}
-__device__ __forceinline__ void dft4(cx& a, cx& b, cx& c, cx& d) {
-    const cx t0 = cadd(a, c), t1 = csub(a, c), t2 = cadd(b, d), t3 = csub(b, d);
-    a = cadd(t0, t2);
-    c = csub(t0, t2);
-    b = {t1.re + t3.im, t1.im - t3.re};  // t1 - i*t3
-    d = {t1.re - t3.im, t1.im + t3.re};  // t1 + i*t3
-}
-__device__ __forceinline__ void dft4(cx (&v)[4]) { dft4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ void dft8(cx (&v)[8]) {
-    constexpr float R2 = 0.70710678118654752f;
-    dft4(v[0], v[2], v[4], v[6]);   // E[0..3] left at v[0], v[2], v[4], v[6]
-    dft4(v[1], v[3], v[5], v[7]);   // O[0..3] left at v[1], v[3], v[5], v[7]
-    const cx o0 = v[1];
-    const cx o1 = {R2 * (v[3].re + v[3].im), R2 * (v[3].im - v[3].re)};      // * W8^1 = (1 - i)/sqrt 2
-    const cx o2 = {v[5].im, -v[5].re};                                        // * W8^2 = -i
-    const cx o3 = {R2 * (v[7].im - v[7].re), -R2 * (v[7].re + v[7].im)};     // * W8^3 = (-1 - i)/sqrt 2
-    const cx e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
-    v[0] = cadd(e0, o0); v[4] = csub(e0, o0);
-    v[1] = cadd(e1, o1); v[5] = csub(e1, o1);
-    v[2] = cadd(e2, o2); v[6] = csub(e2, o2);
-    v[3] = cadd(e3, o3); v[7] = csub(e3, o3);
-}
-template <int R>
-__device__ __forceinline__ void dftR(cx (&v)[R]) {
-    if constexpr (R == 8) dft8(v);
-    else if constexpr (R == 4) dft4(v);
-    else dft2(v);
-}
 
 // One Stockham pass of radix R over M points held by one wavefront: butterfly j (of M/R) takes the inputs
 // j + t*M/R, multiplies input t by W_(NS*R)^(k*t) with k = j mod NS (NS = product of the radices before this pass),
@@ -137,6 +100,58 @@ __device__ __forceinline__ void fft_passes(int lane, float* z, const float* tw, 
     }
 }
 
+// ---- what the power-of-two kernel and the mixed-radix / Bluestein kernel share --------------------------------------
+// One frame's source: complex point m = (x[2m], x[2m+1]) of the windowed frame (torch: frames * window, fp32), with
+// center=True's n_fft/2 samples of reflection on each side.
+struct FrameSrc {
+    const float* w;     // the clip
+    const float* win;   // n_fft window values
+    long s0, L;
+    bool inner;         // no reflection anywhere in this frame
+    __device__ __forceinline__ FrameSrc(const AnyParams& p, long clip, int t, const float* win_)
+        : w(p.wave + clip * p.wave_stride), win(win_), s0((long)t * p.hop - p.n_fft / 2), L(p.L) {
+        inner = s0 >= 0 && s0 + p.n_fft <= p.L;
+    }
+    __device__ __forceinline__ cx operator()(int m) const {
+        float v[2];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            long q = s0 + 2 * m + e;
+            if (!inner) {
+                if (q < 0) q = -q;                      // reflect, no edge repeat
+                if (q >= L) q = 2 * (L - 1) - q;
+                if (q < 0) q = 0;
+                if (q >= L) q = L - 1;
+            }
+            v[e] = w[q] * win[2 * m + e];
+        }
+        return {v[0], v[1]};
+    }
+};
+
+struct WaveBarrier {
+    __device__ __forceinline__ void operator()() const { __builtin_amdgcn_wave_barrier(); }
+};
+
+// Z (M complex points, natural order) -> the M + 1 power bins
+__device__ __forceinline__ void untangle_frame(int lane, int M, const float* z, const float* twn, float* pw) {
+    untangle_lanes(Lanes{lane, lane + 1}, M, z, twn, pw, WaveBarrier{});
+}
+
+// banded mel dot products, 10 log10, store in either layout
+__device__ __forceinline__ void mel_db_store(int lane, const AnyParams& p, const float* pw, long g, long clip, int t) {
+    for (int m = lane; m < p.n_mels; m += 64) {
+        const float* wt = p.fb_wts + p.fb_off[m];
+        const int st = p.fb_start[m], ln = p.fb_len[m];
+        float acc = 0.0f;
+        for (int q = 0; q < ln; q++) acc = __builtin_fmaf(pw[st + q], wt[q], acc);
+        const float db = !(acc <= 1e-10f) ? 10.0f * log10f(acc) : -100.0f;   // (a NaN power stays NaN, as torch.clamp leaves it)
+        if (p.frame_major) p.out[g * p.n_mels + m] = db;
+        else p.out[(clip * p.n_mels + m) * p.T + t] = db;
+    }
+    __builtin_amdgcn_wave_barrier();   // the next frame overwrites the buffers
+}
+
 template <int LOG2M>
 __global__ void __launch_bounds__(WG) logmel_any_kernel(AnyParams p) {
     constexpr int M = 1 << LOG2M, N = 2 * M;
@@ -156,54 +171,51 @@ __global__ void __launch_bounds__(WG) logmel_any_kernel(AnyParams p) {
     for (long g = (long)blockIdx.x * (WG / 64) + wave; g < p.n_frames; g += (long)gridDim.x * (WG / 64)) {
         const long clip = g / p.T;
         const int t = (int)(g - clip * p.T);
-        const float* w = p.wave + clip * p.wave_stride;
-        const long s0 = (long)t * p.hop - M;              // center=True: n_fft/2 samples of reflection on each side
-        const bool inner = s0 >= 0 && s0 + N <= p.L;      // no reflection anywhere in this frame
-        // complex point m = (x[2m], x[2m+1]) of the windowed frame (torch: frames * window, fp32)
-        auto load = [&](int m) -> cx {
-            float v[2];
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                long q = s0 + 2 * m + e;
-                if (!inner) {
-                    if (q < 0) q = -q;                      // reflect, no edge repeat
-                    if (q >= p.L) q = 2 * (p.L - 1) - q;
-                    if (q < 0) q = 0;
-                    if (q >= p.L) q = p.L - 1;
-                }
-                v[e] = w[q] * win[2 * m + e];
-            }
-            return {v[0], v[1]};
-        };
+        const FrameSrc load(p, clip, t, win);
         fft_passes<M, 1, true>(lane, z, tw, load);
-        // even / odd untangling: X[k] = Ev + W_N^k * Od, Ev = (Z[k] + conj Z[M-k]) / 2, Od = -i (Z[k] - conj Z[M-k]) / 2
-        for (int k = lane; k < M; k += 64) {
-            const int kk = (M - k) & (M - 1);
-            const float ar = z[2 * k], ai = z[2 * k + 1];
-            const float br = z[2 * kk], bi = -z[2 * kk + 1];
-            const float evr = 0.5f * (ar + br), evi = 0.5f * (ai + bi);
-            const float dfr = 0.5f * (ar - br), dfi = 0.5f * (ai - bi);
-            const float odr = dfi, odi = -dfr;
-            const float wr = twn[2 * k], wi = twn[2 * k + 1];
-            const float xr = evr + __builtin_fmaf(odr, wr, -(odi * wi));
-            const float xi = evi + __builtin_fmaf(odr, wi, odi * wr);
-            pw[k] = __builtin_fmaf(xr, xr, xi * xi);
-            if (k == 0) {
-                const float nq = ar - ai;                   // X[n_fft/2] = Re Z0 - Im Z0 (purely real)
-                pw[M] = nq * nq;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (int m = lane; m < p.n_mels; m += 64) {
-            const float* wt = p.fb_wts + p.fb_off[m];
-            const int st = p.fb_start[m], ln = p.fb_len[m];
-            float acc = 0.0f;
-            for (int q = 0; q < ln; q++) acc = __builtin_fmaf(pw[st + q], wt[q], acc);
-            const float db = !(acc <= 1e-10f) ? 10.0f * log10f(acc) : -100.0f;   // (a NaN power stays NaN, as torch.clamp leaves it)
-            if (p.frame_major) p.out[g * p.n_mels + m] = db;
-            else p.out[(clip * p.n_mels + m) * p.T + t] = db;
-        }
-        __builtin_amdgcn_wave_barrier();   // the next frame overwrites z / pw
+        untangle_frame(lane, M, z, twn, pw);
+        mel_db_store(lane, p, pw, g, clip, t);
+    }
+}
+
+// Every even n_fft that is not a power of two (logmel_mixed_core.h).  BLUE = false: form 1, the M-point transform as
+// mixed-radix Stockham passes.  BLUE = true: form 2, Bluestein's chirp transform with two P-point power-of-two
+// transforms.  A pass reads one of the wave's two buffers and writes the other (the first pass of a transform reads
+// its input where it lies: global memory, or the product with the filter's transform), so a lane never has to hold
+// more than one butterfly; a wavefront's LDS instructions execute in order and the wave barriers keep the compiler
+// from moving an access across a pass boundary.  The window stays in global memory (read once per sample, coalesced):
+// two P-point buffers per wave are what the LDS is spent on.  blockDim.x / 64 waves per workgroup (1 .. 4, by LDS).
+struct MixedParams {
+    AnyParams a;
+    int P, npass;
+    unsigned long long packed;   // lmx::Plan::packed
+    const float* twp;            // P x (cos, -sin) of 2*pi*q/P
+    const float* chirp;          // form 2: M x w[n]
+    const float* bhat;           // form 2: P x transform of the chirp filter, / P
+};
+
+// (__launch_bounds__(WG) is the upper bound: the launch uses 64 .. 256 threads, launch_mixed)
+template <bool BLUE>
+__global__ void __launch_bounds__(WG) logmel_mixed_kernel(MixedParams p) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];   // W_P (2P) | W_N (2M) | per wave: two buffers of 2P
+    const int M = p.a.n_fft / 2, P = p.P;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    float* tw = sm;
+    float* twn = sm + 2 * P;
+    for (int i = threadIdx.x; i < 2 * P; i += blockDim.x) tw[i] = p.twp[i];
+    for (int i = threadIdx.x; i < 2 * M; i += blockDim.x) twn[i] = p.a.twn[i];
+    __syncthreads();
+    float* buf = sm + 2 * P + 2 * M + (size_t)wave * 4 * P;
+    for (long g = (long)blockIdx.x * nw + wave; g < p.a.n_frames; g += (long)gridDim.x * nw) {
+        const long clip = g / p.a.T;
+        const int t = (int)(g - clip * p.a.T);
+        const FrameSrc src(p.a, clip, t, p.a.win);
+        float* cur = buf;           // after a transform: its result; the first pass of a transform writes `oth`
+        float* oth = buf + 2 * P;
+        const Lanes me{lane, lane + 1};
+        frame_transform<BLUE>(me, M, P, p.npass, p.packed, tw, p.chirp, p.bhat, src, cur, oth, WaveBarrier{});
+        untangle_lanes(me, M, cur, twn, oth, WaveBarrier{});
+        mel_db_store(lane, p.a, oth, g, clip, t);
     }
 }
 
@@ -223,17 +235,41 @@ int launch_any(at_ctx* ctx, const AnyParams& p, hipStream_t stream) {
     return AT_OK;
 }
 
+template <bool BLUE>
+int launch_mixed(at_ctx* ctx, const MixedParams& p, hipStream_t stream) {
+    const size_t M = p.a.n_fft / 2, P = p.P;
+    // as many waves per workgroup (at most four) as leave it inside a CU's 160 KiB of LDS
+    const size_t tabs = (2 * P + 2 * M) * sizeof(float), per_wave = 4 * P * sizeof(float);
+    int nw = WG / 64;
+    while (nw > 1 && tabs + nw * per_wave > 160 * 1024) nw--;
+    const size_t lds = tabs + nw * per_wave;
+    if (lds > 160 * 1024) return at_fail(AT_E_INVALID, "at_logmel_f32: n_fft=%d needs %zu bytes of LDS", p.a.n_fft, lds);
+    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&logmel_mixed_kernel<BLUE>), lds); if (rcl_) return rcl_; }
+    long per_cu = (long)(160 * 1024 / lds);   // persistent, as the power-of-two kernel
+    if (per_cu > 8) per_cu = 8;
+    long grid = per_cu * ctx->n_cus;
+    const long need = (p.a.n_frames + nw - 1) / nw;
+    if (grid > need) grid = need;
+    AT_LAUNCH(logmel_mixed_kernel<BLUE>, dim3((unsigned)grid), dim3(64 * nw), lds, stream, p);
+    return AT_OK;
+}
+
 }  // namespace
 
-// Tables for (sample_rate, n_fft, n_mels, filterbank values): window | W_M | W_N | start, len, off | band weights.
+// Tables for (sample_rate, n_fft, n_mels, filterbank values, form): window | W_M | W_N | form 2: W_P, chirp, filter
+// transform | start, len, off | band weights.  Form 0 = a power of two (logmel_any_kernel), else lmx::Plan::form.
 int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, int64_t wave_stride, int sample_rate,
                   int n_fft, int hop, int n_mels, const float* fb_user_dev, float* out, int frame_major,
                   hipStream_t stream) {
     const int N = n_fft, M = N / 2, NBIN = M + 1;
     int log2m = 0;
     while ((1 << log2m) < M) log2m++;
+    const bool pow2 = (N & (N - 1)) == 0;
+    const Plan plan = make_plan(N, ctx->dbg.logmel_fallback != 0);
+    const int form = pow2 ? 0 : plan.form;
+    const int P = plan.P;
     std::vector<float> fb((size_t)NBIN * n_mels);
-    bool cached = ctx->ws[WS_LOGMEL_ANY] && ctx->any_sr == sample_rate && ctx->any_nfft == n_fft && ctx->any_nmels == n_mels &&
+    bool cached = ctx->ws[WS_LOGMEL_ANY] && ctx->any_sr == sample_rate && ctx->any_nfft == n_fft && ctx->any_nmels == n_mels && ctx->any_form == form &&
                   (ctx->any_user_copy != nullptr) == (fb_user_dev != nullptr);
     if (fb_user_dev) {   // a caller's filterbank is compared by value, never trusted by address (see logmel.hip)
         AT_HIP(hipStreamSynchronize(stream));
@@ -241,7 +277,8 @@ int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, in
         cached = cached && std::memcmp(ctx->any_user_copy, fb.data(), fb.size() * sizeof(float)) == 0;
     }
     const size_t nint = ((size_t)3 * n_mels + 3) & ~(size_t)3;
-    const size_t head = (size_t)N + 2 * (size_t)M + 2 * (size_t)M;   // floats: window, W_M (M complex), W_N (M complex)
+    const size_t head0 = (size_t)N + 2 * (size_t)M + 2 * (size_t)M;   // floats: window, W_M (M complex), W_N (M complex)
+    const size_t head = head0 + (form == FORM_BLUESTEIN ? 2 * (size_t)P + 2 * (size_t)M + 2 * (size_t)P : 0);
     const size_t cap = (head + nint + (size_t)NBIN * n_mels) * 4;
     char* base = static_cast<char*>(at_ws(ctx, WS_LOGMEL_ANY, cap, stream));
     if (!base) return AT_E_NOMEM;
@@ -253,13 +290,11 @@ int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, in
         }
         std::vector<float> blob(head + nint, 0.0f);
         for (int i = 0; i < N; i++) blob[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / N));   // periodic Hann
-        for (int j = 0; j < M; j++) {
-            blob[N + 2 * j] = (float)std::cos(2.0 * M_PI * j / M);
-            blob[N + 2 * j + 1] = (float)-std::sin(2.0 * M_PI * j / M);
-        }
-        for (int k = 0; k < M; k++) {
-            blob[N + 2 * M + 2 * k] = (float)std::cos(2.0 * M_PI * k / N);
-            blob[N + 2 * M + 2 * k + 1] = (float)-std::sin(2.0 * M_PI * k / N);
+        twiddle_table(M, blob.data() + N);              // the builders the host harness checks (logmel_mixed_core.h)
+        untangle_table(N, blob.data() + N + 2 * M);
+        if (form == FORM_BLUESTEIN) {
+            twiddle_table(P, blob.data() + head0);
+            bluestein_tables(M, P, blob.data() + head0 + 2 * P, blob.data() + head0 + 2 * P + 2 * M);
         }
         int* ints = reinterpret_cast<int*>(blob.data() + head);
         std::vector<float> wts;
@@ -282,7 +317,7 @@ int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, in
             if (!ctx->any_user_copy) return at_fail(AT_E_NOMEM, "at_logmel_f32: out of host memory");
             std::memcpy(ctx->any_user_copy, fb.data(), fb.size() * sizeof(float));
         }
-        ctx->any_sr = sample_rate; ctx->any_nfft = n_fft; ctx->any_nmels = n_mels;
+        ctx->any_sr = sample_rate; ctx->any_nfft = n_fft; ctx->any_nmels = n_mels; ctx->any_form = form;
     }
     AnyParams p;
     const float* f = reinterpret_cast<const float*>(base);
@@ -296,6 +331,15 @@ int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, in
     p.fb_start = ints; p.fb_len = ints + n_mels; p.fb_off = ints + 2 * n_mels;
     p.fb_wts = reinterpret_cast<const float*>(ints + nint);
     p.out = out; p.frame_major = frame_major;
+    if (form != 0) {
+        MixedParams mp;
+        mp.a = p;
+        mp.P = P; mp.npass = plan.npass; mp.packed = plan.packed;
+        mp.twp = form == FORM_BLUESTEIN ? f + head0 : p.twm;
+        mp.chirp = f + head0 + 2 * P;
+        mp.bhat = f + head0 + 2 * P + 2 * M;
+        return form == FORM_BLUESTEIN ? launch_mixed<true>(ctx, mp, stream) : launch_mixed<false>(ctx, mp, stream);
+    }
     switch (log2m) {
         case 5: return launch_any<5>(ctx, p, stream);
         case 6: return launch_any<6>(ctx, p, stream);

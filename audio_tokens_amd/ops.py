@@ -51,7 +51,8 @@ def normalize_rows(x, backend=None):
 class LogMelSpectrogram:
     """MelSpectrogram(sample_rate, n_mels, n_fft, hop_length) followed by AmplitudeToDB(), fused.
 
-    __call__(waveform [..., L]) -> [..., n_mels, T] float32 in dB (torchaudio's layout)."""
+    __call__(waveform [..., L]) -> [..., n_mels, T] float32 in dB (torchaudio's layout).
+    n_fft: any even size from 64 to 4096 (400, torchaudio's own default, included); odd sizes are rejected."""
 
     def __init__(self, sample_rate=22050, n_fft=512, hop_length=128, n_mels=64, fb=None, backend=None):
         self.sample_rate, self.n_fft, self.hop_length, self.n_mels = sample_rate, n_fft, hop_length, n_mels

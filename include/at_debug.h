@@ -8,7 +8,10 @@
  *                                 from the environment again; names:
  *                                   assign_variant filter_fused filter_sync prune_kernel prune_nb filter_screen
  *                                   filter_nb filter_wps2 dmin_kernel resample_simple accum_buckets filter_stats visit_bits
- *                                   filter_timing strict_errors
+ *                                   filter_timing logmel_fallback strict_errors
+ *                                 (logmel_fallback = 1 is the one switch that does NOT keep the bits: the even n_fft that
+ *                                 are not powers of two all take the Bluestein form of the transform, so that it can be
+ *                                 held against the mixed-radix form at the sizes that have both; same tolerance)
  *                                 (filter_stats = 1 makes the fp16-split sweeps count for the two calls below: one record
  *                                 per workgroup and a small reduction kernel behind every sweep; off by default)
  *                                 filter_timing = 1 brackets the stage-1 kernel of every exact call with two timing events
