@@ -1114,7 +1114,7 @@ int launch_mfma(at_ctx* ctx, const float* x, int64_t n, const float* c, int k, i
     const size_t lds = 2 * sizeof(float) * tile_floats(D, NA);
     const int64_t rows_per_wg = 4 * 32 * NB;
     const int64_t grid = (n + rows_per_wg - 1) / rows_per_wg;
-    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&assign_mfma_kernel<D, NB, NA, DMA, WPS, SPEC>), lds); if (rcl_) return rcl_; }
+    AT_RAISE_LDS(ctx, (assign_mfma_kernel<D, NB, NA, DMA, WPS, SPEC>), lds);
     AT_LAUNCH((assign_mfma_kernel<D, NB, NA, DMA, WPS, SPEC>), dim3((unsigned)grid), dim3(WG), lds,
                        stream, x, (long)n, img, ntiles, reinterpret_cast<long*>(ids), dist);
     return AT_OK;
@@ -1131,7 +1131,7 @@ static int launch_anyd(at_ctx* ctx, const float* x, int64_t n, int d, const floa
     if (!img) return AT_E_NOMEM;
     AT_LAUNCH(prep_centroids_chunked_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, d, nchunks, NA, img);
     const size_t lds = 2 * sizeof(float) * (tile_rows(NA) * DC + CN_PAD);
-    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&assign_mfma_anyd_kernel<NB, NA, WPS>), lds); if (rcl_) return rcl_; }
+    AT_RAISE_LDS(ctx, (assign_mfma_anyd_kernel<NB, NA, WPS>), lds);
     const int64_t rows_per_wg = 4 * 32 * NB;
     AT_LAUNCH((assign_mfma_anyd_kernel<NB, NA, WPS>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
                        dim3(WG), lds, stream, x, (long)n, d, nchunks, img, ntiles, reinterpret_cast<long*>(ids), dist);
@@ -1220,7 +1220,7 @@ extern "C" int at_assign_hinted_f32(at_ctx* ctx, const float* x, int64_t n, int 
         if (!img) return AT_E_NOMEM;
         AT_LAUNCH(prep_centroids_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, D, D, NA, img);
         const size_t lds = 2 * sizeof(float) * tile_floats(D, NA);
-        { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&assign_mfma_hinted_kernel<D, NB, NA>), lds); if (rcl_) return rcl_; }
+        AT_RAISE_LDS(ctx, (assign_mfma_hinted_kernel<D, NB, NA>), lds);
         const int64_t rows_per_wg = 4 * 32 * NB;
         AT_LAUNCH((assign_mfma_hinted_kernel<D, NB, NA>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
                            dim3(WG), lds, stream, x, (long)n, c, k, img, ntiles, order,
@@ -1233,7 +1233,7 @@ extern "C" int at_assign_hinted_f32(at_ctx* ctx, const float* x, int64_t n, int 
     if (!img) return AT_E_NOMEM;
     AT_LAUNCH(prep_centroids_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, D, D, NA, img);
     const size_t lds = 2 * sizeof(float) * tile_floats(D, NA);
-    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&assign_mfma_hinted_kernel<D, NB, NA>), lds); if (rcl_) return rcl_; }
+    AT_RAISE_LDS(ctx, (assign_mfma_hinted_kernel<D, NB, NA>), lds);
     const int64_t rows_per_wg = 4 * 32 * NB;
     AT_LAUNCH((assign_mfma_hinted_kernel<D, NB, NA>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
                        dim3(WG), lds, stream, x, (long)n, c, k, img, ntiles, order,

@@ -261,6 +261,14 @@ static inline hipError_t at_launch_raw(void (*kern)(KArgs...), dim3 grid, dim3 b
         if (!(cond)) return at_fail(AT_E_INVALID, __VA_ARGS__); \
     } while (0)
 
+// at_raise_lds for a launch of `kernel` with `bytes` of dynamic LDS; returns its error from the calling function.
+// (A template-id with commas goes in parentheses.)
+#define AT_RAISE_LDS(ctx, kernel, bytes)                                                      \
+    do {                                                                                       \
+        const int rc_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&kernel), bytes);      \
+        if (rc_) return rc_;                                                                   \
+    } while (0)
+
 // filter.hip (fp16-split filter of the pruned sweep)
 int at_filter_sweep(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const uint32_t* order,
                     const int32_t* cperm, int ng, const float* bd, const uint32_t* mask, int ngw, int collect,

@@ -187,7 +187,7 @@ int at_l2norm_rows_flagged(at_ctx* ctx, const float* x, int64_t n, int d, float*
     int R = 256;
     while (R > 1 && (size_t)R * (d + 2) * sizeof(float) > 68 * 1024) R >>= 1;
     const size_t lds = (size_t)R * (d + 2) * sizeof(float);
-    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&l2norm_rows_kernel), lds); if (rcl_) return rcl_; }
+    AT_RAISE_LDS(ctx, l2norm_rows_kernel, lds);
     const long blocks = (n + R - 1) / R;
     AT_LAUNCH(l2norm_rows_kernel, dim3((unsigned)blocks), dim3(WG), lds, stream, x, (long)n, d,
                        R, y, bad);

@@ -258,7 +258,7 @@ int at_lloyd_stats_split_f32(at_ctx* ctx, int d, int k, int64_t n, float* hassig
     if (rc) return rc;
     const int p_lds = k <= 16384;
     const size_t lds = p_lds ? (size_t)k * sizeof(float) : 0;
-    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&split_clusters_kernel), lds); if (rcl_) return rcl_; }
+    AT_RAISE_LDS(ctx, split_clusters_kernel, lds);
     AT_LAUNCH(split_clusters_kernel, dim3(1), dim3(WG), lds, stream, d, k, (long)n, hassign, centroids, empties,
                        nsplit_out, raw, (long)raw_n, state_end, p_lds, obj_parts, (long)obj_part_stride, n_parts, stats);
     return AT_OK;

@@ -464,8 +464,8 @@ static int logmel_impl(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t 
     }
     AT_REQUIRE(lds <= 160 * 1024, "at_logmel_f32: n_mels=%d needs %zu bytes of LDS", n_mels, lds);
     const bool pf = ((p.fpb - 1) * hop + NFFT + 3) / 4 <= PREFETCH_REGS * WG;   // the block's samples fit the prefetch registers
-    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&logmel_kernel<true>), lds); if (rcl_) return rcl_; }
-    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&logmel_kernel<false>), lds); if (rcl_) return rcl_; }
+    AT_RAISE_LDS(ctx, logmel_kernel<true>, lds);
+    AT_RAISE_LDS(ctx, logmel_kernel<false>, lds);
     p.blocks_per_clip = (int)((T + p.fpb - 1) / p.fpb);
     p.n_blocks = (long)p.blocks_per_clip * n_clips;
     // persistent workgroups: two per CU (what the LDS footprint allows), each walking a strided share

@@ -223,7 +223,7 @@ template <int LOG2M>
 int launch_any(at_ctx* ctx, const AnyParams& p, hipStream_t stream) {
     constexpr int M = 1 << LOG2M, N = 2 * M;
     const size_t lds = ((size_t)6 * M + (size_t)(WG / 64) * (N + M + 4)) * sizeof(float);
-    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&logmel_any_kernel<LOG2M>), lds); if (rcl_) return rcl_; }
+    AT_RAISE_LDS(ctx, logmel_any_kernel<LOG2M>, lds);
     // persistent: as many workgroups as fit the LDS of the chip (at most eight per CU), each wave walking frames
     long per_cu = (long)(160 * 1024 / lds);
     if (per_cu < 1) per_cu = 1;
@@ -244,7 +244,7 @@ int launch_mixed(at_ctx* ctx, const MixedParams& p, hipStream_t stream) {
     while (nw > 1 && tabs + nw * per_wave > 160 * 1024) nw--;
     const size_t lds = tabs + nw * per_wave;
     if (lds > 160 * 1024) return at_fail(AT_E_INVALID, "at_logmel_f32: n_fft=%d needs %zu bytes of LDS", p.a.n_fft, lds);
-    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&logmel_mixed_kernel<BLUE>), lds); if (rcl_) return rcl_; }
+    AT_RAISE_LDS(ctx, logmel_mixed_kernel<BLUE>, lds);
     long per_cu = (long)(160 * 1024 / lds);   // persistent, as the power-of-two kernel
     if (per_cu > 8) per_cu = 8;
     long grid = per_cu * ctx->n_cus;

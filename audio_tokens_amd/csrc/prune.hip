@@ -20,14 +20,8 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "at_internal.h"
-
-// Onesweep radix sort at every size: below a million items rocPRIM would switch to a merge sort of ~18
-// small launches, which is what an iteration of a sharded (N-GPU) run would then mostly consist of;
-// the keys here are 13-21 bits wide, two or three onesweep passes.
-using at_radix_config = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>;
+#include "at_sort.h"
 
 namespace {
 
@@ -426,11 +420,7 @@ int at_visit_order_f32(at_ctx* ctx, const int64_t* ids, const float* dis, int64_
     const unsigned bits = cbits + (unsigned)dbits;
     rocprim::double_buffer<uint32_t> kb(keys_a, keys_b);
     rocprim::double_buffer<uint32_t> vb(vals_a, vals_b);
-    size_t tmp_bytes = 0;
-    AT_HIP(rocprim::radix_sort_pairs<at_radix_config>(nullptr, tmp_bytes, kb, vb, (size_t)n, 0, bits, stream));
-    void* tmp = at_ws(ctx, WS_VISIT_TMP, tmp_bytes, stream);
-    if (!tmp) return AT_E_NOMEM;
-    AT_HIP(rocprim::radix_sort_pairs<at_radix_config>(tmp, tmp_bytes, kb, vb, (size_t)n, 0, bits, stream));
+    { const int rc = at_sort_pairs(ctx, WS_VISIT_TMP, kb, vb, (size_t)n, 0, bits, stream); if (rc != AT_OK) return rc; }
     AT_LAUNCH(key_to_hint_kernel, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, stream, kb.current(),
                        vb.current(), (long)n, hint_sorted_out, order_out, dbits);
     return AT_OK;

@@ -23,14 +23,11 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "at_internal.h"
+#include "at_sort.h"
 #include "mt19937_dev.h"
 
 namespace {
-
-using perm_radix_config = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>;
 
 // raw[q] = the q-th output of std::mt19937(seed), q in [0, count).
 // state_out (624 words, may be null): the generator's state after the last whole block of 624 outputs, i.e. what
@@ -165,11 +162,7 @@ extern "C" int at_rand_perm_prefix_device(at_ctx* ctx, int64_t n, int64_t seed, 
         while (bits < 32 && (uint64_t(1) << bits) <= (uint64_t)n) bits++;
         rocprim::double_buffer<uint32_t> kbuf(ka, kb);
         rocprim::double_buffer<uint32_t> vbuf(va, vb);
-        size_t tmp_bytes = 0;
-        AT_HIP(rocprim::radix_sort_pairs<perm_radix_config>(nullptr, tmp_bytes, kbuf, vbuf, (size_t)steps, 0, bits, stream));
-        void* tmp = at_ws(ctx, WS_PERM_TMP, tmp_bytes, stream);
-        if (!tmp) return AT_E_NOMEM;
-        AT_HIP(rocprim::radix_sort_pairs<perm_radix_config>(tmp, tmp_bytes, kbuf, vbuf, (size_t)steps, 0, bits, stream));
+        { const int rc = at_sort_pairs(ctx, WS_PERM_TMP, kbuf, vbuf, (size_t)steps, 0, (unsigned)bits, stream); if (rc != AT_OK) return rc; }
         AT_LAUNCH(perm_links_kernel, dim3(gs), dim3(tb), 0, stream, kbuf.current(), vbuf.current(), steps, n, m, prev, last);
     }
     AT_LAUNCH(perm_resolve_kernel, dim3((unsigned)((m + tb - 1) / tb)), dim3(tb), 0, stream, raw, prev, last, steps, n, m, prefix);

@@ -26,9 +26,8 @@
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "at_internal.h"
+#include "at_sort.h"
 
 namespace {
 
@@ -44,9 +43,6 @@ constexpr size_t LDS_Q = (size_t)QW * LS * 4;
 constexpr size_t LDS_J = (size_t)JC * LS * 4;
 constexpr size_t LDS_D = (size_t)(WG / 64) * JC * DSTR * 4;
 constexpr size_t LDS_BYTES = LDS_Q + LDS_J + LDS_D + (size_t)JC * 8;
-
-// the library's rocPRIM sort configuration (kmeans.hip, prune.hip)
-using at_radix_config = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>;
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
@@ -247,7 +243,7 @@ extern "C" int at_silhouette_f32(at_ctx* ctx, const float* x, int d, const int64
     AT_LAUNCH(sil_head_kernel, dim3(blocks), dim3(WG), 0, stream, keys, n, head);
     AT_HIP(rocprim::inclusive_scan(tmp, scan_bytes, head, seg, (size_t)n, rocprim::plus<uint32_t>(), stream));
     AT_LAUNCH(sil_segments_kernel, dim3(blocks), dim3(WG), 0, stream, x, d, n, perm, head, seg, off, nrm, n_labels);
-    { const int rcl_ = at_raise_lds(ctx, reinterpret_cast<const void*>(&silhouette_kernel), LDS_BYTES); if (rcl_) return rcl_; }
+    AT_RAISE_LDS(ctx, silhouette_kernel, LDS_BYTES);
     AT_LAUNCH(silhouette_kernel, dim3((unsigned)((n + QW - 1) / QW)), dim3(WG), LDS_BYTES, stream, x, d, n, perm, seg, off,
               nrm, s);
     AT_HIP(hipEventRecord(ctx->sil_ev, stream));
