@@ -308,6 +308,58 @@ def test_gather_rows(be):
         assert np.array_equal(got, x[idx])
 
 
+@pytest.mark.parametrize("op,d", [("gather_rows", 64), ("l2norm_rows", 64), ("assign", 40), ("assign", 80), ("assign", 640),
+                                  ("assign_refuses", 64), ("assign_refuses", 128), ("search_k", 64)])
+def test_rows_that_are_not_16_byte_aligned(be, oracle, op, d):
+    """d % 4 == 0 and rows one float off a 16-byte boundary: at_gather_rows_f32, at_l2norm_rows_f32, at_assign_f32 (generic
+    d) and at_knn_f32 leave their 16-byte loads for the scalar branch -- the reference's bits, and the aligned call's;
+    at_assign_f32 at d = 64 / 128 has no such branch and says so."""
+    from audio_tokens_amd import _lib
+    from audio_tokens_amd.ops import IndexFlatL2
+    from device_rows import rows_one_float_off
+    from knn_ref import knn_ref
+    rng = np.random.default_rng(d + len(op))
+    n = 1500
+    x = _unit_rows(rng, n, d, oracle)
+    xa, xu = be._f32(x), rows_one_float_off(x, be.device)
+    assert xa.data_ptr() % 16 == 0 and torch.equal(xa, xu)
+    if op == "gather_rows":
+        idx = rng.integers(0, n, 333).astype(np.int32)
+        got = be.gather_rows(xu, idx).cpu().numpy()
+        assert np.array_equal(bits(got), bits(x[idx]))
+        assert np.array_equal(bits(got), bits(be.gather_rows(xa, idx).cpu().numpy()))
+    elif op == "l2norm_rows":
+        x = (x * rng.uniform(1e-3, 1e2, (n, 1))).astype(np.float32)
+        x[3] = 0.0
+        xa, xu = be._f32(x), rows_one_float_off(x, be.device)
+        ref = x / (np.linalg.norm(x, axis=1, keepdims=True) + 1e-10)
+        got = be.l2norm_rows(xu).cpu().numpy()
+        assert ref.dtype == np.float32 and np.array_equal(bits(got), bits(ref))
+        assert np.array_equal(bits(got), bits(be.l2norm_rows(xa).cpu().numpy()))
+    elif op == "assign":
+        c = _unit_rows(rng, 300, d, oracle)
+        ids_o, dis_o = oracle.assign(x, c)
+        for xt in (xu, xa):
+            ids, dis = be.assign(xt, c)
+            assert np.array_equal(ids.cpu().numpy(), ids_o)
+            assert np.array_equal(bits(dis.cpu().numpy()), bits(dis_o))
+    elif op == "assign_refuses":
+        c = _unit_rows(rng, 300, d, oracle)
+        with pytest.raises(_lib.NativeError, match="at_assign_f32: x must be 16-byte aligned"):
+            be.assign(xu, c)
+        ids_o, dis_o = oracle.assign(x, c)                       # (and the context is fine afterwards)
+        ids, dis = be.assign(xa, c)
+        assert np.array_equal(ids.cpu().numpy(), ids_o) and np.array_equal(bits(dis.cpu().numpy()), bits(dis_o))
+    else:
+        c = _unit_rows(rng, 200, d, oracle)
+        index = IndexFlatL2(d, backend=be)
+        index.add(c)
+        Dr, Ir = knn_ref(oracle, x, c, 5)
+        for xt in (xu, xa):
+            D, I = index.search(xt, 5)
+            assert np.array_equal(I.cpu().numpy(), Ir) and np.array_equal(bits(D.cpu().numpy()), bits(Dr))
+
+
 @pytest.mark.parametrize("n,d,k", [(5000, 64, 37), (20000, 64, 500), (3000, 128, 64), (2000, 640, 10), (1000, 8, 5)])
 def test_centroid_accum_is_the_sequential_sum(be, n, d, k):
     rng = np.random.default_rng(n + d + k)
