@@ -5,8 +5,11 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <functional>
 #include <tuple>
 #include <utility>
+#include <vector>
 
 #include "../../include/audio_tokens_amd.h"
 #include "../../include/at_debug.h"
@@ -113,20 +116,29 @@ struct at_debug {
     int filter_timing;    // AT_FILTER_TIMING    1 = exact calls bracket their stage-1 kernel with two timing events (bench.py; off in the product)
 };
 
+// What a log-mel table slot holds (WS_LOGMEL_FB: the tuned 512-point kernel's tables; WS_LOGMEL_ANY: every other
+// n_fft's).  All zero = the slot holds nothing a call may use; fields a path does not use stay 0.
+struct at_logmel_tables {
+    int sr, nfft, nmels, hop, form;   // the key (hop: the 512 path's quad / plain decision depends on it; form: 0 power
+                                      // of two, 1 mixed radix, 2 Bluestein)
+    int nw, quads;                    // derived, 512 path: number of band weights, bands stored as 4-aligned quads
+    float* user_copy;                 // malloc'd host copy of the caller's filterbank the tables were built from
+                                      // (compared by value per call); null = the library's own filterbank
+};
+static inline void at_logmel_tables_clear(at_logmel_tables* t) {
+    std::free(t->user_copy);
+    *t = at_logmel_tables{};
+}
+
 struct at_ctx {
     int device;
     at_debug dbg;
     void* ws[WS_NSLOTS];
     size_t ws_bytes[WS_NSLOTS];
-    // cached description of what WS_LOGMEL_FB currently holds
-    int fb_sr, fb_nfft, fb_nmels, fb_nw, fb_hop, fb_quads;
-    const float* fb_user;
+    at_logmel_tables lm_fb, lm_any;   // what WS_LOGMEL_FB / WS_LOGMEL_ANY currently hold
     hipEvent_t mt_ready;   // behind the generation of WS_MT_RAW
     int mt_have;
     uint32_t mt_seed;
-    int any_sr, any_nfft, any_nmels, any_form;   // what WS_LOGMEL_ANY holds (form: 0 power of two, 1 mixed radix, 2 Bluestein)
-    float* any_user_copy;
-    float* fb_user_copy;   // host copy of the user filterbank the tables were built from (malloc'd; compared per call)
     int n_cus;             // multiProcessorCount of the device (read once in at_create)
     int rs_orig, rs_new;  // what WS_RESAMPLE_TAPS currently holds
     int64_t filter_rows, filter_listed;  // fp16-split filter: rows swept / rows handed to the fp32 redo
@@ -299,6 +311,24 @@ int at_filter_redo_rows(at_ctx* ctx, const float* x, int d, const float* c, int 
                         const uint32_t* order, const int32_t* cperm, const float* dmin, int ng, const unsigned* misc,
                         const uint32_t* aux, int64_t* ids, float* dist, const unsigned* count_dev, unsigned amb_cap,
                         hipStream_t stream);
+
+// logmel.hip: the resident tables of a log-mel slot for `key` (sr, nfft, nmels, hop, form; the rest 0) and the caller's
+// filterbank (device [nfft/2 + 1][nmels], compared by value) or the library's own (null); *tabs = the slot's device pointer.
+// On a miss `build` makes the blob (at most cap_bytes) from the filterbank values on the host -- its head, then
+// lmt::pack_bands (logmel_tables.h) -- and sets the derived fields of the record it is handed, a copy of the key.
+typedef std::function<void(const float* fb, std::vector<float>& blob, at_logmel_tables* t)> at_logmel_builder;
+int at_logmel_resident(at_ctx* ctx, int slot, at_logmel_tables* rec, const at_logmel_tables& key, size_t cap_bytes,
+                       const float* fb_user_dev, hipStream_t stream, const at_logmel_builder& build, const float** tabs);
+
+// center=True's reflect padding as an index into a clip of L samples: reflect, no edge repeat, then clamp (the clamp
+// is only reachable for frames past T, which are never stored)
+__device__ __forceinline__ long reflect_index(long q, long L) {
+    if (q < 0) q = -q;
+    if (q >= L) q = 2 * (L - 1) - q;
+    if (q < 0) q = 0;
+    if (q >= L) q = L - 1;
+    return q;
+}
 
 // logmel_any.hip: every even n_fft other than 512
 int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, int64_t wave_stride, int sample_rate,

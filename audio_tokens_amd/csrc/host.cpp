@@ -186,8 +186,8 @@ void at_destroy(at_ctx* ctx) {
     if (ctx->sil_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sil_ev));
     if (ctx->knn_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->knn_ev));
     if (ctx->filter_host_misc) (void)AT_HIP_TOLERATE(hipHostFree(ctx->filter_host_misc));
-    std::free(ctx->fb_user_copy);
-    std::free(ctx->any_user_copy);
+    at_logmel_tables_clear(&ctx->lm_fb);
+    at_logmel_tables_clear(&ctx->lm_any);
     (void)AT_HIP_TOLERATE(hipSetDevice(prev));
     delete ctx;
 }
@@ -254,12 +254,12 @@ void* at_ws(at_ctx* ctx, int slot, size_t bytes, hipStream_t stream) {
     }
     ctx->ws[slot] = p;
     ctx->ws_bytes[slot] = want;
-    if (slot == WS_LOGMEL_FB) { ctx->fb_sr = ctx->fb_nfft = ctx->fb_nmels = 0; ctx->fb_user = nullptr; }
+    if (slot == WS_LOGMEL_FB) at_logmel_tables_clear(&ctx->lm_fb);
     if (slot == WS_RESAMPLE_TAPS) ctx->rs_orig = ctx->rs_new = 0;
     if (slot == WS_MT_RAW) ctx->mt_have = 0;
     if (slot == WS_LONG_PRED) ctx->long_pred_k = 0;
     if (slot == WS_BUCKETS) ctx->buckets_k = 0;
-    if (slot == WS_LOGMEL_ANY) ctx->any_nfft = 0;
+    if (slot == WS_LOGMEL_ANY) at_logmel_tables_clear(&ctx->lm_any);
     return p;
 }
 

@@ -18,11 +18,13 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "at_internal.h"
 #include "l2norm_core.h"
 #include "logmel_core.h"
+#include "logmel_tables.h"
 
 namespace {
 
@@ -158,12 +160,7 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
                 if (i4 < nsamp4) {
 #pragma unroll
                     for (int e = 0; e < 4; e++) {
-                        long q = s0 + 4 * i4 + e;
-                        if (q < 0) q = -q;                      // reflect, no edge repeat
-                        if (q >= p.L) q = 2 * (p.L - 1) - q;
-                        if (q < 0) q = 0;                       // only reachable for frames past T (never stored)
-                        if (q >= p.L) q = p.L - 1;
-                        pre[j][e] = w[q];
+                        pre[j][e] = w[reflect_index(s0 + 4 * i4 + e, p.L)];
                     }
                 }
             }
@@ -183,14 +180,7 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
         } else {
             const float* w = p.wave + clip * p.wave_stride;
             const long s0 = (long)t0 * p.hop - NFFT / 2;
-            for (int i = tid; i < nsamp; i += WG) {
-                long q = s0 + i;
-                if (q < 0) q = -q;                      // reflect, no edge repeat
-                if (q >= p.L) q = 2 * (p.L - 1) - q;
-                if (q < 0) q = 0;                       // only reachable for frames past T (never stored)
-                if (q >= p.L) q = p.L - 1;
-                samp[i] = w[q];
-            }
+            for (int i = tid; i < nsamp; i += WG) samp[i] = w[reflect_index(s0 + i, p.L)];
         }
         __syncthreads();  // samples in place; the previous block's staged output has been stored by everybody
         if constexpr (PF)
@@ -298,7 +288,6 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
     }
 }
 
-// Host side: window / twiddles / banded filterbank, uploaded once per (sr, n_mels, fb) change.
 // LDS bytes of one workgroup of `fpb` frames (kernel layout), with `fb_ints` words of filterbank tables
 size_t lds_bytes(int fpb, int hop, int n_mels, size_t fb_ints) {
     const int nsamp = (fpb - 1) * hop + NFFT;
@@ -307,103 +296,79 @@ size_t lds_bytes(int fpb, int hop, int n_mels, size_t fb_ints) {
 }
 constexpr size_t LDS_TWO_PER_CU = 80 * 1024;  // two workgroups of this size share a CU
 
-int build_tables(at_ctx* ctx, int sample_rate, int n_mels, int hop, const float* fb_user_dev, hipStream_t stream,
-                 const float** tabs, const int** st, const int** ln, const int** of, const float** wt,
-                 int* n_weights, int* quads) {
-    bool cached = ctx->ws[WS_LOGMEL_FB] && ctx->fb_sr == sample_rate && ctx->fb_nfft == NFFT &&
-                  ctx->fb_nmels == n_mels && (ctx->fb_user != nullptr) == (fb_user_dev != nullptr) && ctx->fb_hop == hop;
-    std::vector<float> fb((size_t)NBIN * n_mels);
-    if (fb_user_dev) {
-        // A caller's filterbank is never trusted by address (allocators hand the same address to the next
-        // tensor of the same shape, and a tensor can be rewritten in place): its VALUES are read back and
-        // compared with the copy the resident tables were built from.  66 KB and one stream synchronisation
-        // per call -- the price of the option; the library's own filterbank (fb_or_null == NULL) pays nothing.
-        AT_HIP(hipStreamSynchronize(stream));
-        AT_HIP(hipMemcpy(fb.data(), fb_user_dev, fb.size() * sizeof(float), hipMemcpyDeviceToHost));
-        cached = cached && ctx->fb_user_copy && std::memcmp(ctx->fb_user_copy, fb.data(), fb.size() * sizeof(float)) == 0;
+// The blob of WS_LOGMEL_FB (an at_logmel_builder; `t` holds the key, and receives nw and quads): window | W256
+// twiddles | W512 twiddles, then the banded filterbank (logmel_tables.h).  Bands padded with zero weights to whole
+// 4-aligned quads of bins (16-byte LDS reads, see logmel_core.h mel_band) -- unless the padding is what pushes a
+// 32-frame workgroup past half a CU's LDS, in which case the bands are stored as they are.  (A dense user filterbank,
+// too big for LDS either way, stays in global memory: quads.)
+void build_tables_512(const float* fb, std::vector<float>& blob, at_logmel_tables* t) {
+    blob.assign(TAB_FLOATS, 0.0f);
+    lmt::hann_periodic(NFFT, &blob[TAB_WIN]);
+    for (int j = 0; j < 256; j++) {
+        const int e = (j / 16) * (j % 16);  // layout [k1][m2] -> W256^(m2*k1) (logmel_core.h phase1)
+        blob[TAB_TW256 + 2 * j] = (float)std::cos(2.0 * M_PI * e / 256.0);
+        blob[TAB_TW256 + 2 * j + 1] = (float)-std::sin(2.0 * M_PI * e / 256.0);
+        blob[TAB_TW512 + 2 * j] = (float)std::cos(2.0 * M_PI * j / 512.0);
+        blob[TAB_TW512 + 2 * j + 1] = (float)-std::sin(2.0 * M_PI * j / 512.0);
     }
-    std::vector<int> start(n_mels), len(n_mels), off(n_mels);
-    std::vector<float> wts;
-    size_t bytes = 0;
-    char* base = nullptr;
-    if (!cached) {
-        if (!fb_user_dev) {
-            int rc = at_mel_filterbank_host(sample_rate, NFFT, n_mels, fb.data());
-            if (rc) return rc;
-        }
-        // Bands padded with zero weights to whole 4-aligned quads of bins (16-byte LDS reads, see
-        // logmel_core.h mel_band) -- unless the padding is what pushes a 32-frame workgroup past half
-        // a CU's LDS, in which case the bands are stored as they are.
-        const size_t nint0 = ((size_t)3 * n_mels + 3) & ~(size_t)3;
-        for (int gran = 4; gran >= 1; gran -= 3) {
-            wts.clear();
-            for (int m = 0; m < n_mels; m++) {
-                int lo = NBIN, hi = -1;
-                for (int f = 0; f < NBIN; f++)
-                    if (fb[(size_t)f * n_mels + m] != 0.0f) { lo = f < lo ? f : lo; hi = f; }
-                const int s4 = hi < 0 ? 0 : (lo / gran) * gran;
-                const int e4 = hi < 0 ? 0 : ((hi + gran) / gran) * gran;
-                start[m] = s4;
-                len[m] = (e4 - s4) / gran;
-                off[m] = (int)wts.size();
-                for (int f = s4; f < e4; f++) wts.push_back(f < NBIN ? fb[(size_t)f * n_mels + m] : 0.0f);
-            }
-            ctx->fb_quads = gran == 4;
-            const bool fits = lds_bytes(32, hop, n_mels, nint0 + wts.size()) <= LDS_TWO_PER_CU;
-            const bool lds_ok = (nint0 + wts.size()) * 4 <= 14 * 1024;
-            if (gran == 1 || fits || !lds_ok) break;  // (a dense user filterbank stays in global memory: quads)
-        }
+    for (int gran = 4;; gran = 1) {
+        t->nw = (int)lmt::pack_bands(blob, TAB_FLOATS, fb, NBIN, t->nmels, gran);
+        t->quads = gran == 4;
+        const size_t words = lmt::table_ints(t->nmels) + t->nw;
+        if (gran == 1 || lds_bytes(32, t->hop, t->nmels, words) <= LDS_TWO_PER_CU || words * 4 > 14 * 1024) break;
     }
-    // layout: [tabs TAB_FLOATS f32][start4 n_mels i32][quads][off][pad to 4 ints][wts ...]; worst case all bins
-    const size_t nint = ((size_t)3 * n_mels + 3) & ~(size_t)3;
-    const size_t cap = sizeof(float) * TAB_FLOATS + sizeof(int) * nint + sizeof(float) * (size_t)(NBIN + 3) * n_mels;
-    if (!cached) {
-        base = static_cast<char*>(at_ws(ctx, WS_LOGMEL_FB, cap, stream));
-        if (!base) return AT_E_NOMEM;
-        std::vector<float> t(TAB_FLOATS);
-        for (int i = 0; i < NFFT; i++) t[TAB_WIN + i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / NFFT));
-        for (int j = 0; j < 256; j++) {
-            const int e = (j / 16) * (j % 16);  // layout [k1][m2] -> W256^(m2*k1) (logmel_core.h phase1)
-            t[TAB_TW256 + 2 * j] = (float)std::cos(2.0 * M_PI * e / 256.0);
-            t[TAB_TW256 + 2 * j + 1] = (float)-std::sin(2.0 * M_PI * e / 256.0);
-            t[TAB_TW512 + 2 * j] = (float)std::cos(2.0 * M_PI * j / 512.0);
-            t[TAB_TW512 + 2 * j + 1] = (float)-std::sin(2.0 * M_PI * j / 512.0);
-        }
-        std::vector<char> blob(sizeof(float) * TAB_FLOATS + sizeof(int) * nint + sizeof(float) * wts.size(), 0);
-        char* q = blob.data();
-        std::memcpy(q, t.data(), sizeof(float) * TAB_FLOATS); q += sizeof(float) * TAB_FLOATS;
-        std::memcpy(q, start.data(), sizeof(int) * n_mels); q += sizeof(int) * n_mels;
-        std::memcpy(q, len.data(), sizeof(int) * n_mels); q += sizeof(int) * n_mels;
-        std::memcpy(q, off.data(), sizeof(int) * n_mels); q += sizeof(int) * n_mels;
-        q = blob.data() + sizeof(float) * TAB_FLOATS + sizeof(int) * nint;
-        if (!wts.empty()) std::memcpy(q, wts.data(), sizeof(float) * wts.size());
-        bytes = blob.size();
-        // a launch on ANY stream may still be reading the tables about to be replaced
-        AT_HIP(hipDeviceSynchronize());
-        AT_HIP(hipMemcpy(base, blob.data(), bytes, hipMemcpyHostToDevice));
-        std::free(ctx->fb_user_copy);
-        ctx->fb_user_copy = nullptr;
-        if (fb_user_dev) {
-            ctx->fb_user_copy = static_cast<float*>(std::malloc(fb.size() * sizeof(float)));
-            if (!ctx->fb_user_copy) return at_fail(AT_E_NOMEM, "at_logmel_f32: out of host memory");
-            std::memcpy(ctx->fb_user_copy, fb.data(), fb.size() * sizeof(float));
-        }
-        ctx->fb_sr = sample_rate; ctx->fb_nfft = NFFT; ctx->fb_nmels = n_mels; ctx->fb_user = fb_user_dev;
-        ctx->fb_nw = (int)wts.size();
-        ctx->fb_hop = hop;
-    } else {
-        base = static_cast<char*>(ctx->ws[WS_LOGMEL_FB]);
-    }
-    *tabs = reinterpret_cast<const float*>(base);
-    const int* ints = reinterpret_cast<const int*>(base + sizeof(float) * TAB_FLOATS);
-    *st = ints; *ln = ints + n_mels; *of = ints + 2 * n_mels;
-    *wt = reinterpret_cast<const float*>(ints + nint);
-    *n_weights = ctx->fb_nw;
-    *quads = ctx->fb_quads;
-    return AT_OK;
 }
 
 }  // namespace
+
+int at_logmel_resident(at_ctx* ctx, int slot, at_logmel_tables* rec, const at_logmel_tables& key, size_t cap_bytes,
+                       const float* fb_user_dev, hipStream_t stream, const at_logmel_builder& build, const float** tabs) {
+    const size_t fb_floats = (size_t)(key.nfft / 2 + 1) * key.nmels, fb_bytes = fb_floats * sizeof(float);
+    std::vector<float> fb;
+    if (fb_user_dev) {
+        // A caller's filterbank is never trusted by address (allocators hand the same address to the next tensor of
+        // the same shape, and a tensor can be rewritten in place): its VALUES are read back and compared with the copy
+        // the resident tables were built from.  66 KB at 512 x 64 and one stream synchronisation per call -- the price
+        // of the option; the library's own filterbank (fb_or_null == NULL) pays nothing.
+        fb.resize(fb_floats);
+        AT_HIP(hipStreamSynchronize(stream));
+        AT_HIP(hipMemcpy(fb.data(), fb_user_dev, fb_bytes, hipMemcpyDeviceToHost));
+    }
+    // (a slot that at_ws regrew, or that a failed call left in flux, has an all-zero record: nmels = 0 matches no call)
+    const bool hit = ctx->ws[slot] && rec->sr == key.sr && rec->nfft == key.nfft && rec->nmels == key.nmels &&
+                     rec->hop == key.hop && rec->form == key.form && (rec->user_copy != nullptr) == (fb_user_dev != nullptr) &&
+                     (!fb_user_dev || std::memcmp(rec->user_copy, fb.data(), fb_bytes) == 0);
+    if (hit) {
+        *tabs = static_cast<const float*>(ctx->ws[slot]);
+        return AT_OK;
+    }
+    if (!fb_user_dev) {
+        fb.resize(fb_floats);
+        int rc = at_mel_filterbank_host(key.sr, key.nfft, key.nmels, fb.data());
+        if (rc) return rc;
+    }
+    // Everything that can fail for want of memory comes first, while the slot and its record are still whole ...
+    std::vector<float> blob;
+    at_logmel_tables filled = key;
+    build(fb.data(), blob, &filled);
+    std::unique_ptr<float, decltype(&std::free)> copy(nullptr, &std::free);
+    if (fb_user_dev) {
+        copy.reset(static_cast<float*>(std::malloc(fb_bytes)));
+        if (!copy) return at_fail(AT_E_NOMEM, "at_logmel_f32: out of host memory");
+        std::memcpy(copy.get(), fb.data(), fb_bytes);
+    }
+    float* dev = static_cast<float*>(at_ws(ctx, slot, cap_bytes, stream));
+    if (!dev) return AT_E_NOMEM;
+    // ... then the record describes nothing for as long as the tables on the device are in flux: a call that fails in
+    // between leaves a slot the next call rebuilds, never new tables under the old key.
+    at_logmel_tables_clear(rec);
+    AT_HIP(hipDeviceSynchronize());   // a launch on ANY stream may still be reading the tables about to be replaced
+    AT_HIP(hipMemcpy(dev, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
+    *rec = filled;                    // (nothing between the copy and these two lines can fail)
+    rec->user_copy = copy.release();
+    *tabs = dev;
+    return AT_OK;
+}
 
 static int logmel_impl(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L,
                        int64_t wave_stride, int sample_rate, int n_fft, int hop, int n_mels,
@@ -438,9 +403,16 @@ static int logmel_impl(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t 
     }
 
     LogmelParams p;
-    int rc = build_tables(ctx, sample_rate, n_mels, hop, fb_or_null, stream, &p.tabs, &p.fb_start, &p.fb_len,
-                          &p.fb_off, &p.fb_wts, &p.fb_nw, &p.fb_quads);
+    const at_logmel_tables key{sample_rate, NFFT, n_mels, hop, /* form */ 0};
+    const lmt::BlobLayout lay = lmt::blob_layout(TAB_FLOATS, n_mels);
+    // (capacity: the worst case, every bin of every filter and its quad padding)
+    int rc = at_logmel_resident(ctx, WS_LOGMEL_FB, &ctx->lm_fb, key, (lay.wts + (size_t)(NBIN + 3) * n_mels) * 4, fb_or_null,
+                                stream, build_tables_512, &p.tabs);
     if (rc) return rc;
+    p.fb_start = reinterpret_cast<const int*>(p.tabs + lay.ints);
+    p.fb_len = p.fb_start + n_mels; p.fb_off = p.fb_start + 2 * n_mels;
+    p.fb_wts = p.tabs + lay.wts;
+    p.fb_nw = ctx->lm_fb.nw; p.fb_quads = ctx->lm_fb.quads;
     const int64_t T = at_num_frames(L, hop);
     AT_REQUIRE(T < (1LL << 31), "at_logmel_f32: too many frames per clip");
     p.wave = wave; p.n_clips = n_clips; p.L = L; p.wave_stride = wave_stride;
@@ -453,7 +425,7 @@ static int logmel_impl(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t 
     if (fuse_l2norm && !p.bad) return AT_E_NOMEM;
     p.minmax = minmax;
     // the banded filterbank rides in LDS too unless a dense user filterbank makes it too big
-    const size_t fb_ints = (((size_t)3 * n_mels + 3) & ~(size_t)3) + p.fb_nw;
+    const size_t fb_ints = lmt::table_ints(n_mels) + p.fb_nw;
     p.fb_lds = fb_ints * 4 <= 14 * 1024;
     // 32 frames per workgroup when two workgroups of that size still share a CU's 160 KiB of LDS
     // (the kernel is latency-bound: one workgroup per CU runs at half the rate), else 16
@@ -496,22 +468,19 @@ extern "C" int at_logmel_minmax_f32(at_ctx* ctx, const float* wave, int64_t n_cl
     hipStream_t stream = (hipStream_t)stream_;
     AT_REQUIRE(ctx, "at_logmel_minmax_f32: ctx is null");
     if (n_clips == 0) return AT_OK;
-    AT_REQUIRE(hop >= 1, "at_logmel_minmax_f32: hop=%d out of range", hop);
-    const int64_t clip_elems = at_num_frames(L, hop) * n_mels;
-    if (n_fft != NFFT) {
-        int rc = logmel_impl(ctx, wave, n_clips, L, wave_stride, sample_rate, n_fft, hop, n_mels, fb_or_null, out, layout, 0,
-                             nullptr, stream);
-        if (rc) return rc;
-        return at_minmax_scale_clips_f32(ctx, out, n_clips, clip_elems, stream_);
+    unsigned* mm = nullptr;
+    if (n_fft == NFFT) {   // the fused form: the kernel collects the extremes
+        AT_REQUIRE(n_clips <= 65535, "at_logmel_minmax_f32: at most 65535 clips per call");
+        AT_HIP(hipSetDevice(ctx->device));
+        mm = static_cast<unsigned*>(at_ws(ctx, WS_LOGMEL_MINMAX, (size_t)n_clips * 16, stream));
+        if (!mm) return AT_E_NOMEM;
+        AT_LAUNCH(minmax_init_kernel, dim3((unsigned)((n_clips + 255) / 256)), dim3(256), 0, stream, mm, (long)n_clips);
     }
-    AT_REQUIRE(n_clips <= 65535, "at_logmel_minmax_f32: at most 65535 clips per call");
-    AT_HIP(hipSetDevice(ctx->device));
-    unsigned* mm = static_cast<unsigned*>(at_ws(ctx, WS_LOGMEL_MINMAX, (size_t)n_clips * 16, stream));
-    if (!mm) return AT_E_NOMEM;
-    AT_LAUNCH(minmax_init_kernel, dim3((unsigned)((n_clips + 255) / 256)), dim3(256), 0, stream, mm, (long)n_clips);
     int rc = logmel_impl(ctx, wave, n_clips, L, wave_stride, sample_rate, n_fft, hop, n_mels, fb_or_null, out, layout, 0, mm,
                          stream);
     if (rc) return rc;
+    const int64_t clip_elems = at_num_frames(L, hop) * n_mels;   // (logmel_impl has checked every argument by now)
+    if (!mm) return at_minmax_scale_clips_f32(ctx, out, n_clips, clip_elems, stream_);
     int bx = (int)((clip_elems + 256 * 8 - 1) / (256 * 8));
     if (bx < 1) bx = 1;
     if (bx > 64) bx = 64;

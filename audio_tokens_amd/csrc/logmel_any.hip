@@ -14,12 +14,11 @@
 // radices from {8, 4, 2, 3, 5, 7} where M has no larger prime factor, Bluestein's chirp transform elsewhere
 // (logmel_mixed_core.h; tests/test_gpu_logmel_nfft.py).
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "at_internal.h"
 #include "logmel_mixed_core.h"
+#include "logmel_tables.h"
 
 namespace {
 
@@ -117,12 +116,7 @@ struct FrameSrc {
 #pragma unroll
         for (int e = 0; e < 2; e++) {
             long q = s0 + 2 * m + e;
-            if (!inner) {
-                if (q < 0) q = -q;                      // reflect, no edge repeat
-                if (q >= L) q = 2 * (L - 1) - q;
-                if (q < 0) q = 0;
-                if (q >= L) q = L - 1;
-            }
+            if (!inner) q = reflect_index(q, L);
             v[e] = w[q] * win[2 * m + e];
         }
         return {v[0], v[1]};
@@ -268,68 +262,35 @@ int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, in
     const Plan plan = make_plan(N, ctx->dbg.logmel_fallback != 0);
     const int form = pow2 ? 0 : plan.form;
     const int P = plan.P;
-    std::vector<float> fb((size_t)NBIN * n_mels);
-    bool cached = ctx->ws[WS_LOGMEL_ANY] && ctx->any_sr == sample_rate && ctx->any_nfft == n_fft && ctx->any_nmels == n_mels && ctx->any_form == form &&
-                  (ctx->any_user_copy != nullptr) == (fb_user_dev != nullptr);
-    if (fb_user_dev) {   // a caller's filterbank is compared by value, never trusted by address (see logmel.hip)
-        AT_HIP(hipStreamSynchronize(stream));
-        AT_HIP(hipMemcpy(fb.data(), fb_user_dev, fb.size() * sizeof(float), hipMemcpyDeviceToHost));
-        cached = cached && std::memcmp(ctx->any_user_copy, fb.data(), fb.size() * sizeof(float)) == 0;
-    }
-    const size_t nint = ((size_t)3 * n_mels + 3) & ~(size_t)3;
     const size_t head0 = (size_t)N + 2 * (size_t)M + 2 * (size_t)M;   // floats: window, W_M (M complex), W_N (M complex)
     const size_t head = head0 + (form == FORM_BLUESTEIN ? 2 * (size_t)P + 2 * (size_t)M + 2 * (size_t)P : 0);
-    const size_t cap = (head + nint + (size_t)NBIN * n_mels) * 4;
-    char* base = static_cast<char*>(at_ws(ctx, WS_LOGMEL_ANY, cap, stream));
-    if (!base) return AT_E_NOMEM;
-    if (ctx->any_nfft != n_fft) cached = false;   // (a grown slot forgets what it held)
-    if (!cached) {
-        if (!fb_user_dev) {
-            int rc = at_mel_filterbank_host(sample_rate, n_fft, n_mels, fb.data());
-            if (rc) return rc;
-        }
-        std::vector<float> blob(head + nint, 0.0f);
-        for (int i = 0; i < N; i++) blob[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / N));   // periodic Hann
+    const lmt::BlobLayout lay = lmt::blob_layout(head, n_mels);
+    const at_logmel_tables key{sample_rate, n_fft, n_mels, /* hop */ 0, form};
+    const at_logmel_builder build = [&](const float* fb, std::vector<float>& blob, at_logmel_tables*) {
+        blob.assign(head, 0.0f);
+        lmt::hann_periodic(N, blob.data());
         twiddle_table(M, blob.data() + N);              // the builders the host harness checks (logmel_mixed_core.h)
         untangle_table(N, blob.data() + N + 2 * M);
         if (form == FORM_BLUESTEIN) {
             twiddle_table(P, blob.data() + head0);
             bluestein_tables(M, P, blob.data() + head0 + 2 * P, blob.data() + head0 + 2 * P + 2 * M);
         }
-        int* ints = reinterpret_cast<int*>(blob.data() + head);
-        std::vector<float> wts;
-        for (int m = 0; m < n_mels; m++) {
-            int lo = NBIN, hi = -1;
-            for (int f = 0; f < NBIN; f++)
-                if (fb[(size_t)f * n_mels + m] != 0.0f) { lo = f < lo ? f : lo; hi = f; }
-            ints[m] = hi < 0 ? 0 : lo;
-            ints[n_mels + m] = hi < 0 ? 0 : hi - lo + 1;
-            ints[2 * n_mels + m] = (int)wts.size();
-            for (int f = lo; f <= hi; f++) wts.push_back(fb[(size_t)f * n_mels + m]);
-        }
-        blob.insert(blob.end(), wts.begin(), wts.end());
-        AT_HIP(hipDeviceSynchronize());   // a launch on any stream may still be reading the tables about to be replaced
-        AT_HIP(hipMemcpy(base, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
-        std::free(ctx->any_user_copy);
-        ctx->any_user_copy = nullptr;
-        if (fb_user_dev) {
-            ctx->any_user_copy = static_cast<float*>(std::malloc(fb.size() * sizeof(float)));
-            if (!ctx->any_user_copy) return at_fail(AT_E_NOMEM, "at_logmel_f32: out of host memory");
-            std::memcpy(ctx->any_user_copy, fb.data(), fb.size() * sizeof(float));
-        }
-        ctx->any_sr = sample_rate; ctx->any_nfft = n_fft; ctx->any_nmels = n_mels; ctx->any_form = form;
-    }
+        lmt::pack_bands(blob, head, fb, NBIN, n_mels, 1);
+    };
+    const float* f = nullptr;
+    int rc = at_logmel_resident(ctx, WS_LOGMEL_ANY, &ctx->lm_any, key, (lay.wts + (size_t)NBIN * n_mels) * 4, fb_user_dev,
+                                stream, build, &f);
+    if (rc) return rc;
     AnyParams p;
-    const float* f = reinterpret_cast<const float*>(base);
     p.wave = wave; p.n_clips = n_clips; p.L = L; p.wave_stride = wave_stride;
     p.n_fft = N; p.log2m = log2m; p.hop = hop; p.n_mels = n_mels;
     const int64_t T = at_num_frames(L, hop);
     p.T = (int)T;
     p.n_frames = n_clips * T;
     p.win = f; p.twm = f + N; p.twn = f + N + 2 * M;
-    const int* ints = reinterpret_cast<const int*>(f + head);
-    p.fb_start = ints; p.fb_len = ints + n_mels; p.fb_off = ints + 2 * n_mels;
-    p.fb_wts = reinterpret_cast<const float*>(ints + nint);
+    p.fb_start = reinterpret_cast<const int*>(f + lay.ints);
+    p.fb_len = p.fb_start + n_mels; p.fb_off = p.fb_start + 2 * n_mels;
+    p.fb_wts = f + lay.wts;
     p.out = out; p.frame_major = frame_major;
     if (form != 0) {
         MixedParams mp;

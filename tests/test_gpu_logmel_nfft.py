@@ -217,3 +217,42 @@ def test_two_streams_share_the_table_slot(be):
         assert torch.equal(be.logmel(a, SR, 400, 160, 64).view(torch.int32), want400.view(torch.int32))
         assert torch.equal(be.logmel(a, SR, 1024, 256, 64).view(torch.int32), want1024.view(torch.int32))
         assert torch.equal(be.logmel(a, SR, 2038, 512, 64).view(torch.int32), want2038.view(torch.int32))
+
+
+def test_table_cache_transitions(be, oracle):
+    """Twelve calls that walk both table slots through every change of their key -- hop (the input of the quad / plain
+    decision), n_mels, sample rate, a caller's filterbank and back, n_fft within the general slot, the form (mixed
+    radix, power of two, Bluestein) -- run twice on the session backend: every result equals, bit for bit, the same
+    single call on a backend whose context has just been created and holds no tables.  (HipBackend() shares the
+    process-wide context of its device, resident tables included, so the cold backend is given a context of its own;
+    the calls that name only (n_fft, hop, n_mels) run at 22050 Hz.)"""
+    from audio_tokens_amd import _lib
+    from audio_tokens_amd.backend import HipBackend
+    clips = torch.from_numpy(test_clips(512, 128, L=6000, n=2)).to(be.device)
+    own, rev = False, True
+    calls = [(22050, 512, 128, 64, own), (22050, 512, 400, 64, own), (22050, 512, 400, 136, own),
+             (16000, 512, 400, 136, own), (16000, 512, 400, 136, rev), (16000, 512, 400, 136, own),
+             (SR, 400, 160, 64, own), (SR, 400, 160, 64, rev), (SR, 1024, 256, 64, own), (SR, 2038, 512, 64, own),
+             (SR, 400, 160, 40, own), (22050, 512, 128, 64, own)]
+
+    def run(backend, sr, n_fft, hop, n_mels, user):
+        fb = oracle.mel_filterbank(sr, n_fft, n_mels)[:, ::-1].copy() if user else None
+        out = backend.logmel(clips, sr, n_fft, hop, n_mels, fb=fb)
+        assert tuple(out.shape) == (2, n_mels, 1 + 6000 // hop)
+        return out.view(torch.int32)
+
+    want = {}
+    for c in calls:
+        if c not in want:                                  # one cold context per distinct call, used once
+            cold = HipBackend(be.device)
+            cold.ctx = _lib.Context(be.device.index)
+            assert cold.ctx.handle.value != be.ctx.handle.value
+            try:
+                want[c] = run(cold, *c)
+                torch.cuda.synchronize()
+            finally:
+                cold.ctx.close()
+    assert len(want) == 10
+    for rnd in range(2):
+        for i, c in enumerate(calls):
+            assert torch.equal(run(be, *c), want[c]), f"round {rnd}, call {i + 1}: {c}"
