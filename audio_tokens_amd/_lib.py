@@ -25,6 +25,21 @@ class PrunedArgs(_c.Structure):
                 ("prepass_done", _i32), ("image_current", _i32), ("ids", _vp), ("dist_or_null", _vp)]
 
 
+class FlacInfo(_c.Structure):
+    """struct at_flac_info of include/audio_tokens_amd.h."""
+    _fields_ = [("channels", _c.c_int32), ("bits_per_sample", _c.c_int32), ("sample_rate", _c.c_int32),
+                ("min_block", _c.c_int32), ("max_block", _c.c_int32), ("variable_blocksize", _c.c_int32),
+                ("total_samples", _i64)]
+
+
+# struct at_flac_frame as a numpy record (64 bytes): the frame tables are numpy arrays, uploaded as they are
+FLAC_FRAME_FIELDS = [("offset", "<i8"), ("first_sample", "<i8"), ("out_base", "<i8"), ("out_stride", "<i8"),
+                     ("length", "<i4"), ("block_size", "<i4"), ("channel_assignment", "<i4"), ("bits_per_sample", "<i4"),
+                     ("header_bytes", "<i4"), ("channels", "<i4"), ("clip", "<i4"), ("reserved", "<i4")]
+
+AT_E_FLAC_NOT_FLAC, AT_E_FLAC_UNSUPPORTED, AT_E_FLAC_CORRUPT = -7, -8, -9
+
+
 # name -> (restype, argtypes); kept in one table so tests can check every declared symbol exports
 SIGNATURES = {
     "at_version": (_i32, []),
@@ -84,6 +99,8 @@ SIGNATURES = {
     "at_token_stats_f64": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "at_silhouette_f32": (_i32, [_vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "at_knn_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "at_flac_index_host": (_i32, [_vp, _i64, _c.POINTER(FlacInfo), _vp, _i64, _c.POINTER(_i64)]),
+    "at_flac_decode_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -89,6 +89,24 @@ class HostHelpers:
     def resample_length(self, L: int, orig_freq: int, new_freq: int) -> int:
         return int(self.lib.at_resample_length(L, orig_freq, new_freq))
 
+    def flac_index(self, data: bytes):
+        """One FLAC file's bytes -> (facts, frames): facts = {"channels", "bits_per_sample", "sample_rate",
+        "total_samples", "min_block", "max_block", "variable_blocksize"}, frames = numpy records
+        (_lib.FLAC_FRAME_FIELDS: offset, length, first_sample, block_size, channel_assignment, bits_per_sample, ...), one
+        per audio frame, none decoded.  Raises NativeError with code AT_E_FLAC_NOT_FLAC / _UNSUPPORTED / _CORRUPT."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        info, n = _lib.FlacInfo(), ctypes.c_int64(0)
+        cap = max(64, buf.size // 512)
+        while True:
+            frames = np.zeros(cap, dtype=np.dtype(_lib.FLAC_FRAME_FIELDS))
+            _lib.check(self.lib.at_flac_index_host(_np_ptr(buf) if buf.size else _np_ptr(np.zeros(1, np.uint8)), buf.size,
+                                                   ctypes.byref(info), _np_ptr(frames), cap, ctypes.byref(n)))
+            if n.value <= cap:
+                break
+            cap = int(n.value)
+        facts = {name: int(getattr(info, name)) for name, _ in _lib.FlacInfo._fields_}
+        return facts, frames[:n.value]
+
     @staticmethod
     def part_layout(k, d):
         """Packed per-rank partial of one Lloyd iteration, in floats: sums [k*d], counts [k], padding to an even
@@ -302,6 +320,71 @@ class HipBackend(HostHelpers):
                 _lib.check(self.lib.at_resample_f32(self.ctx.handle, _ptr(wave[c0:c1]), c1 - c0, L, wave.stride(0),
                                                     orig_freq, new_freq, _ptr(out[c0:c1]), out.stride(0), self._stream()))
         return out[0] if squeeze else out
+
+    def flac_decode(self, blobs):
+        """FLAC files (bytes each) -> per blob, in order, (float32 [C, L] device tensor, sample_rate), the values
+        torchaudio.load returns, or None for a blob that did not index or decode.  One index pass on the host, ONE upload
+        (the files back to back and the frame table behind them) and three stream operations whatever the number of clips.
+        self.flac_status then holds, per blob, 0, the negative AT_E_FLAC_* code of the indexer or the positive AT_FLAC_*
+        kind of the clip's first failing frame."""
+        self.flac_status = status = [0] * len(blobs)
+        if not blobs:
+            return []
+        host, plan = self._flac_pack(blobs, status)
+        dev = host.to(self.device, non_blocking=True)
+        out, clip_status = self._flac_launch(dev, plan)
+        decoded = clip_status.cpu().tolist()                 # (waits for the decode, and so for the upload)
+        res = []
+        for c, f in enumerate(plan["facts"]):
+            if f is None:
+                res.append(None)
+                continue
+            status[c] = decoded[c]
+            C, L = f[0]["channels"], f[0]["total_samples"]
+            res.append((out[f[2]:f[2] + C * L].view(C, L), f[0]["sample_rate"]) if decoded[c] == 0 else None)
+        return res
+
+    def _flac_pack(self, blobs, status):
+        """Host half of flac_decode: index every blob, then one pinned buffer = the indexed files back to back, 8 zero
+        bytes, and (64-byte aligned) the concatenated frame table.  -> (buffer, plan)."""
+        facts, tables, pos, base = [], [], 0, 0
+        for c, blob in enumerate(blobs):
+            try:
+                f, fr = self.flac_index(blob)
+            except _lib.NativeError as e:
+                if e.code not in (_lib.AT_E_FLAC_NOT_FLAC, _lib.AT_E_FLAC_UNSUPPORTED, _lib.AT_E_FLAC_CORRUPT):
+                    raise
+                status[c] = e.code
+                facts.append(None)
+                continue
+            fr["offset"] += pos
+            fr["clip"], fr["out_base"] = c, base
+            facts.append((f, pos, base))
+            tables.append(fr)
+            pos += len(blob)
+            base += f["channels"] * f["total_samples"]
+        table = np.concatenate(tables) if tables else np.zeros(0, np.dtype(_lib.FLAC_FRAME_FIELDS))
+        table_at = (pos + 8 + 63) // 64 * 64
+        host = torch.zeros(table_at + table.nbytes, dtype=torch.uint8).pin_memory()
+        hv = host.numpy()
+        for blob, f in zip(blobs, facts):
+            if f is not None:
+                hv[f[1]:f[1] + len(blob)] = np.frombuffer(blob, dtype=np.uint8)
+        hv[table_at:] = table.view(np.uint8)
+        return host, {"facts": facts, "data_bytes": pos, "table_at": table_at, "n_frames": len(table),
+                      "n_clips": len(blobs), "out_floats": base}
+
+    def _flac_launch(self, dev, plan, out=None):
+        """Device half: at_flac_decode_f32 on the uploaded buffer -> (out float32 [out_floats], clip_status int32)."""
+        if out is None:
+            out = self.empty(max(plan["out_floats"], 1))
+        frame_status = self.empty(max(plan["n_frames"], 1), dtype=torch.int32)
+        clip_status = self.empty(plan["n_clips"], dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_flac_decode_f32(_ptr(dev), plan["data_bytes"], _vp(dev.data_ptr() + plan["table_at"]),
+                                                   plan["n_frames"], plan["n_clips"], _ptr(out), plan["out_floats"],
+                                                   _ptr(frame_status), _ptr(clip_status), self._stream()))
+        return out, clip_status
 
     def token_histogram(self, ids, k: int) -> torch.Tensor:
         """int64 [k] counts of the token ids (device tensor in, device tensor out)."""

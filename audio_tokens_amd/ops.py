@@ -10,6 +10,8 @@
         (processors/spec_tokenizer.py:123-127, 77)
     sklearn.metrics.silhouette_score                      ->  silhouette_score, silhouette_samples
         (processors/cluster_creator.py:115-117)
+    torchaudio.load (of a .flac file)                     ->  load_flac, load_flac_batch
+        (processors/spectrogram_generator.py:99)
 
 Same constructor arguments, method names, return types and error behaviour as the originals for the
 subset the reference uses.  All arithmetic happens in libaudio_tokens_amd.so (HIP, gfx950); this
@@ -32,7 +34,7 @@ import torch
 from .backend import default_backend
 
 __all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "normalize_rows", "silhouette_samples",
-           "silhouette_score"]
+           "silhouette_score", "load_flac", "load_flac_batch"]
 
 
 def _is_host(x) -> bool:
@@ -46,6 +48,45 @@ def normalize_rows(x, backend=None):
     host = _is_host(x)
     y = be.l2norm_rows(x)
     return be.to_host(y) if host else y
+
+
+class FlacDecodeError(RuntimeError):
+    """The reference's RuntimeError("Failed to decode audio.") with the kind of failure: `status` is the indexer's
+    negative AT_E_FLAC_* code or the decoder's positive AT_FLAC_* kind; `unsupported` = a stream this decoder does not
+    read (Ogg-FLAC, 32-bit samples), which another decoder might."""
+
+    def __init__(self, status):
+        super().__init__("Failed to decode audio.")
+        self.status = int(status)
+        self.unsupported = self.status == -8      # AT_E_FLAC_UNSUPPORTED
+
+
+def _flac_bytes(src):
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        return bytes(src)
+    try:
+        with open(src, "rb") as f:
+            return f.read()
+    except OSError:
+        return b""
+
+
+def load_flac_batch(paths, backend=None):
+    """torchaudio.load for many .flac files (paths, or the files' bytes) in one device decode: per file, in order,
+    (float32 [C, L] device tensor, sample_rate), or None for a file that could not be decoded; the kinds of the
+    failures are left in backend.flac_status."""
+    be = backend or default_backend()
+    return be.flac_decode([_flac_bytes(p) for p in paths])
+
+
+def load_flac(path_or_bytes, backend=None):
+    """torchaudio.load(path) for a .flac file, decoded on the device: (float32 [C, L] device tensor, sample_rate).
+    Any failure raises RuntimeError("Failed to decode audio."), the error the reference skips."""
+    be = backend or default_backend()
+    res = be.flac_decode([_flac_bytes(path_or_bytes)])[0]
+    if res is None:
+        raise FlacDecodeError(be.flac_status[0])
+    return res
 
 
 class LogMelSpectrogram:

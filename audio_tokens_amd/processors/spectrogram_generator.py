@@ -7,8 +7,10 @@ Same constructor, methods, outputs (spectrograms/{train,validation}/<ytid>.npy, 
     STFT -> mel -> dB launch per length (the reference launches a dozen kernels per clip);
   * the whole batch comes back in one device->host copy before the per-file np.save.
   * clips at another sample rate go through the device polyphase resampler (ops.Resample).
-Audio decoding stays on the CPU: torchaudio.load if torchaudio is importable, otherwise PCM/float
-.wav through the standard library and raw float32 .npy waveforms (used by the synthetic tests).
+.flac files are decoded on the device (ops.load_flac / load_flac_batch: all of a batch in one call) and stay there
+through the mono mix and the resampler.  Other audio is decoded on the CPU: torchaudio.load if torchaudio is
+importable, otherwise PCM/float .wav through the standard library and raw float32 .npy waveforms (used by the
+synthetic tests).
 """
 import json
 import logging
@@ -22,7 +24,7 @@ import torch
 from tqdm import tqdm
 
 from ..audio_tokens_config import AudioTokensConfig
-from ..ops import LogMelSpectrogram, Resample
+from ..ops import LogMelSpectrogram, Resample, load_flac, load_flac_batch
 from .dataset_splitter import load_split
 
 try:  # optional: only used for decoding when it exists
@@ -31,10 +33,22 @@ except Exception:  # pragma: no cover - not installed in the build image
     _torchaudio = None
 
 
+_FLAC_UNSUPPORTED = -8   # AT_E_FLAC_UNSUPPORTED (include/audio_tokens_amd.h): a stream another decoder might read
+
+
 def _load_audio(path: Path):
-    """-> (waveform float32 [C, L] on the host, sample_rate).  RuntimeError("Failed to decode audio.")
-    is the one failure the reference skips silently (spectrogram_generator.py:98-103)."""
+    """-> (waveform float32 [C, L], sample_rate); on the host, except for .flac, which is decoded on the device.
+    RuntimeError("Failed to decode audio.") is the one failure the reference skips silently
+    (spectrogram_generator.py:98-103)."""
     suffix = path.suffix.lower()
+    if suffix == ".flac":
+        try:
+            return load_flac(path)
+        except RuntimeError as e:
+            # a stream the native decoder does not read (Ogg-FLAC, 32-bit samples): torchaudio's, where it exists
+            if getattr(e, "unsupported", False) and _torchaudio is not None:
+                return _torchaudio.load(path)
+            raise
     if suffix == ".npy":
         w = np.load(path)
         w = w[None, :] if w.ndim == 1 else w
@@ -104,12 +118,25 @@ class SpectrogramGenerator:
         """-> [{"filename": str, "spec": Tensor[n_mels, T]}] in input order, bad clips skipped.
         The tensors are views of per-length batch results that already live on the host side of
         one bulk copy when `.cpu()` is called on them (they share storage per batch)."""
+        found = [(i, self.find_audio_file(ytid)) for i, ytid in enumerate(source_files)]
+        # the batch's .flac files in one device decode; the waveforms stay on the device
+        be = self.spec_transformer.backend
+        flacs = [p for _, p in found if p and p.suffix.lower() == ".flac"]
+        decoded = dict(zip(flacs, zip(load_flac_batch(flacs, backend=be), be.flac_status))) if flacs else {}
         waves, names = [], []
-        for i, ytid in enumerate(source_files):
-            audio_file_path = self.find_audio_file(ytid)
+        for i, audio_file_path in found:
             if not audio_file_path:
                 continue
-            waveform = self.preprocess_waveform(audio_file_path)
+            if audio_file_path in decoded:
+                got, status = decoded[audio_file_path]
+                if got is None and status == _FLAC_UNSUPPORTED and _torchaudio is not None:
+                    got = _torchaudio.load(audio_file_path)   # (Ogg-FLAC, 32-bit samples: as _load_audio does)
+                if got is None:
+                    self.logger.info(f"skipping {audio_file_path}: Failed to decode audio.")
+                    continue
+                waveform = self.resample(self.convert_to_mono(got[0]), got[1])
+            else:
+                waveform = self.preprocess_waveform(audio_file_path)
             if waveform is None:
                 continue
             waves.append(waveform)

@@ -10,6 +10,8 @@
  *       processors/spectrogram_generator.py:28-34, 123-126
  *   torchaudio.transforms.Resample(sr, 22050)(wave)                        at_resample_f32
  *       processors/spectrogram_generator.py:117-121
+ *   torchaudio.load(path) of a .flac file                                  at_flac_index_host,
+ *       processors/spectrogram_generator.py:99                             at_flac_decode_f32
  *   np.linalg.norm(axis=1) row normalisation                               at_l2norm_rows_f32
  *       processors/cluster_creator.py:64-66, processors/spec_tokenizer.py:106-109
  *   faiss.IndexFlatL2(d).add(c); .search(x, 1)                             at_assign_f32
@@ -357,6 +359,72 @@ int at_silhouette_f32(at_ctx* ctx, const float* x, int d, const int64_t* labels,
  * sort per row.  A call on another stream than the context's previous at_knn_f32 waits for that call. */
 int at_knn_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k_c, int k, int64_t* ids,
                float* dist_or_null, void* stream);
+
+/* ---- FLAC: torchaudio.load(path) for the reference's .flac files (processors/spectrogram_generator.py:99) --------
+ * Native FLAC streams of 1-8 channels and 4-24 bits per sample.  The host finds the frames, the device decodes them:
+ * one record per audio frame, every frame independent of the others. */
+#define AT_E_FLAC_NOT_FLAC (-7)    /* no "fLaC" marker (behind an optional ID3v2 tag) */
+#define AT_E_FLAC_UNSUPPORTED (-8) /* Ogg-encapsulated FLAC, bits per sample above 24 or below 4, STREAMINFO missing */
+#define AT_E_FLAC_CORRUPT (-9)     /* metadata cut short, a frame chain that does not reach STREAMINFO's sample count */
+
+/* status of a frame / a clip after at_flac_decode_f32 (a clip reports the kind of its first failing frame) */
+#define AT_FLAC_OK 0
+#define AT_FLAC_BAD_SUBFRAME 1 /* subframe header: padding bit set, reserved type, wasted bits >= sample width,
+                                  predictor order above the block size */
+#define AT_FLAC_RESERVED 2     /* reserved residual method, LPC precision 1111, negative LPC shift, a partition order
+                                  the block size does not allow */
+#define AT_FLAC_OVERRUN 3      /* the bit reader ran past the frame's bytes */
+#define AT_FLAC_CRC16 4        /* frame CRC-16 mismatch */
+#define AT_FLAC_BAD_RECORD 5   /* the frame record itself points outside the buffers it was given with */
+
+typedef struct at_flac_info {
+    int32_t channels, bits_per_sample, sample_rate;
+    int32_t min_block, max_block;   /* STREAMINFO's block size range */
+    int32_t variable_blocksize;     /* blocking strategy bit of the frames (0 when there are none) */
+    int64_t total_samples;          /* per channel; the sum of the block sizes when STREAMINFO says 0 */
+} at_flac_info;
+
+typedef struct at_flac_frame {
+    int64_t offset;        /* byte offset of the frame's sync code (indexer: in the file; decoder: in `data`) */
+    int64_t first_sample;  /* index of the frame's first sample in its channel row */
+    int64_t out_base;      /* decoder: float index in `out` of the clip's [C][L] block (indexer: 0) */
+    int64_t out_stride;    /* decoder: the clip's row stride L in floats (indexer: total_samples) */
+    int32_t length;        /* bytes up to the next frame or the end of the file: a bound, not the exact frame length */
+    int32_t block_size;    /* samples per channel, 1..65535 */
+    int32_t channel_assignment; /* 0-7: n+1 independent channels, 8 left/side, 9 side/right, 10 mid/side */
+    int32_t bits_per_sample;
+    int32_t header_bytes;  /* length of the frame header, CRC-8 included */
+    int32_t channels;
+    int32_t clip;          /* decoder: which clip_status entry this frame reports to (indexer: 0) */
+    int32_t reserved;
+} at_flac_frame;
+
+/* Reads one file's bytes (HOST): skips a leading ID3v2 tag, requires "fLaC", walks the metadata blocks (STREAMINFO
+ * read, all others ignored) and lists every audio frame without decoding it.  A frame is accepted where the sync
+ * pattern is followed by a header without reserved codes, whose CRC-8 matches, whose channels / sample size / sample
+ * rate agree with STREAMINFO, whose block size is within STREAMINFO's maximum, whose coded number continues the chain
+ * (frame number = previous + 1, or sample number = previous + previous block size, from 0) and which lies at least
+ * STREAMINFO's minimum frame size behind the previous one.  frames_host: capacity records, or NULL with capacity 0;
+ * *n_frames receives the number of frames found, of which min(*n_frames, capacity) were written -- a caller whose
+ * table was too small calls again.  Returns AT_OK, or AT_E_FLAC_* / AT_E_INVALID with a message in at_last_error(). */
+int at_flac_index_host(const uint8_t* data_host, int64_t n_bytes, at_flac_info* info, at_flac_frame* frames_host,
+                       int64_t capacity, int64_t* n_frames);
+
+/* Decodes n_frames frames, one lane each, stream-ordered, on the current device; the caller owns every buffer.
+ *   data: DEVICE bytes, the files of a batch back to back, 4-byte aligned, data_bytes long and followed by at least
+ *     8 more readable bytes;  frames: DEVICE [n_frames], the files' tables concatenated in clip order with offset
+ *     rebased to `data` and clip / out_base / out_stride / channels filled in (n_frames < 2^28);
+ *   out: DEVICE float [out_floats]; clip c's [C][L] block, channel-major, starts at its out_base; each sample is
+ *     sample / 2^(bps-1), exact.  A frame writes only [first_sample, first_sample + block_size) of its rows;
+ *   frame_status: DEVICE int32 [n_frames]; clip_status: DEVICE int32 [n_clips] -- AT_FLAC_*, 0 = every frame decoded
+ *     and its CRC-16 matched.  The samples of a failed frame are unspecified.
+ * Covers constant / verbatim / fixed 0-4 / LPC 1-32 subframes, wasted bits, both Rice methods, every partition
+ * order, escaped partitions, the three stereo decorrelations; LPC sums are 64-bit.  Every loop is bounded by the
+ * record (which is itself checked against data_bytes and out_floats) and no byte outside the 4-byte words that
+ * overlap [offset, offset + length + 4) is read: a malformed frame ends in a status, not in a fault. */
+int at_flac_decode_f32(const uint8_t* data, int64_t data_bytes, const at_flac_frame* frames, int64_t n_frames,
+                       int32_t n_clips, float* out, int64_t out_floats, int32_t* frame_status, int32_t* clip_status,
+                       void* stream);
 
 #ifdef __cplusplus
 }
