@@ -37,6 +37,20 @@ FLAC_FRAME_FIELDS = [("offset", "<i8"), ("first_sample", "<i8"), ("out_base", "<
                      ("length", "<i4"), ("block_size", "<i4"), ("channel_assignment", "<i4"), ("bits_per_sample", "<i4"),
                      ("header_bytes", "<i4"), ("channels", "<i4"), ("clip", "<i4"), ("reserved", "<i4")]
 
+# struct at_frontend_clip_in / at_frontend_clip / at_frontend_group / at_frontend_totals as numpy records: the plan of
+# the ragged front end is made into numpy arrays and uploaded as it is
+FRONTEND_CLIP_IN_FIELDS = [("offset", "<i8"), ("row_stride", "<i8"), ("length", "<i8"), ("channels", "<i4"), ("rate", "<i4")]
+FRONTEND_CLIP_FIELDS = [("in_offset", "<i8"), ("in_row_stride", "<i8"), ("in_length", "<i8"), ("out_length", "<i8"),
+                        ("mono_offset", "<i8"), ("first_frame", "<i8"), ("first_block16", "<i8"), ("first_block32", "<i8"),
+                        ("rs_first_block", "<i8"), ("n_frames", "<i4"), ("channels", "<i4"), ("group", "<i4"),
+                        ("too_short", "<i4")]
+FRONTEND_GROUP_FIELDS = [("first", "<i8"), ("count", "<i8"), ("n_blocks", "<i8"), ("out_per_block", "<i8"),
+                         ("orig_freq", "<i4"), ("new_freq", "<i4"), ("orig", "<i4"), ("nw", "<i4"), ("width", "<i4"),
+                         ("K", "<i4"), ("mode", "<i4"), ("TI", "<i4")]
+FRONTEND_TOTALS_FIELDS = [("mono_floats", "<i8"), ("n_frames", "<i8"), ("n_blocks16", "<i8"), ("n_blocks32", "<i8"),
+                          ("n_short", "<i8"), ("n_groups", "<i8")]
+AT_FRONTEND_COPY, AT_FRONTEND_SIMPLE, AT_FRONTEND_TILED = 0, 1, 2
+
 AT_E_FLAC_NOT_FLAC, AT_E_FLAC_UNSUPPORTED, AT_E_FLAC_CORRUPT = -7, -8, -9
 
 
@@ -101,6 +115,9 @@ SIGNATURES = {
     "at_knn_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "at_flac_index_host": (_i32, [_vp, _i64, _c.POINTER(FlacInfo), _vp, _i64, _c.POINTER(_i64)]),
     "at_flac_decode_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "at_frontend_plan_host": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "at_mix_resample_ragged_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "at_logmel_ragged_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

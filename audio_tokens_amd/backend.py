@@ -107,6 +107,38 @@ class HostHelpers:
         facts = {name: int(getattr(info, name)) for name, _ in _lib.FlacInfo._fields_}
         return facts, frames[:n.value]
 
+    def frontend_plan(self, channels, lengths, rates, common_sr, n_fft, hop, offsets=None, row_strides=None):
+        """at_frontend_plan_host: the layout of a batch of clips of unequal length, channel count (1 or 2) and sample
+        rate -> (plan, order, groups, totals): numpy records per clip (_lib.FRONTEND_CLIP_FIELDS), the clip indices
+        sorted by group, one record per reduced rate pair (_lib.FRONTEND_GROUP_FIELDS) and the int64 totals as a dict.
+        offsets / row_strides (floats) say where every clip's [C, L] block lies in the input buffer; by default the
+        blocks lie back to back."""
+        n = len(lengths)
+        cin = np.zeros(n, np.dtype(_lib.FRONTEND_CLIP_IN_FIELDS))
+        cin["channels"], cin["length"], cin["rate"] = channels, lengths, rates
+        cin["row_stride"] = cin["length"] if row_strides is None else row_strides
+        if offsets is None:
+            sizes = cin["channels"].astype(np.int64) * cin["length"]
+            cin["offset"] = np.cumsum(sizes) - sizes
+        else:
+            cin["offset"] = offsets
+        plan = np.zeros(n, np.dtype(_lib.FRONTEND_CLIP_FIELDS))
+        order = np.zeros(n, np.int32)
+        cap = 16
+        while True:
+            groups = np.zeros(cap, np.dtype(_lib.FRONTEND_GROUP_FIELDS))
+            totals = np.zeros(1, np.dtype(_lib.FRONTEND_TOTALS_FIELDS))
+            try:
+                _lib.check(self.lib.at_frontend_plan_host(_np_ptr(cin), n, common_sr, n_fft, hop, _np_ptr(plan),
+                                                          _np_ptr(order), _np_ptr(groups), cap, _np_ptr(totals)))
+                break
+            except _lib.NativeError as e:
+                if "rate pairs" not in str(e) or cap >= max(n, 16):
+                    raise
+                cap = max(n, 16)
+        tot = {name: int(totals[0][name]) for name, _ in _lib.FRONTEND_TOTALS_FIELDS}
+        return plan, order, groups[:tot["n_groups"]], tot
+
     @staticmethod
     def part_layout(k, d):
         """Packed per-rank partial of one Lloyd iteration, in floats: sums [k*d], counts [k], padding to an even
@@ -144,6 +176,8 @@ class HipBackend(HostHelpers):
         self.assign_trace = None  # set to a list to collect (kind, n, d, k, start_event, end_event)
         self.assign_trace_only = None   # a set of kinds: only those are traced (every traced launch is two events on the stream)
         # host-side A/B switches, read from the environment once (the native ones: at_debug.h, self.debug_set)
+        self.frontend_calls = 0   # native calls of the ragged front end so far (frontend_ragged)
+        self.frontend_bytes = 0   # bytes it uploaded
         self.switches = {"filter": os.environ.get("AT_FILTER", "1") != "0",
                          "c2f_fused": os.environ.get("AT_C2F_FUSED", "1") != "0"}
 
@@ -321,6 +355,92 @@ class HipBackend(HostHelpers):
                                                     orig_freq, new_freq, _ptr(out[c0:c1]), out.stride(0), self._stream()))
         return out[0] if squeeze else out
 
+    def frontend_ragged(self, clips, rates, common_sr, n_fft, hop, n_mels, fb=None, frame_major=False, l2norm=False,
+                        pad_value=None):
+        """Mono mix, resampler and log-mel for a batch of clips of any length, channel count and sample rate: one
+        native call per rate pair present and one log-mel call, whatever the lengths (at_mix_resample_ragged_f32,
+        at_logmel_ragged_f32).  Same bits as torch.mean, resample() and logmel() on each clip alone.
+
+        clips: a list of [C, L] or [L] tensors (device tensors are read where they lie; host tensors are uploaded in
+        one copy; more than two channels are mixed by torch.mean first), or what flac_decode left in self.flac_flat:
+        (flat device buffer, [(offset, C, L), ...]).  rates: one rate or one per clip.
+        -> (out, n_frames, first_frame, bad): out is flat, clip i's [n_mels, T_i] block at n_mels * first_frame[i]
+        (frame_major: [sum T_i, n_mels], rows first_frame[i] .. + T_i); n_frames (int32) and first_frame (int64) are
+        numpy arrays, T_i = 0 for a clip too short for the reflect padding (resampled length <= n_fft / 2); bad is a
+        device int32 [n_clips], non-zero where the clip's output holds a NaN or Inf.  pad_value (tests): what the
+        intermediate buffer's padding between clips is filled with."""
+        if isinstance(clips, tuple):
+            flat, table = clips
+            clips = [flat[o:o + C * L].view(C, L) for o, C, L in table]
+        n = len(clips)
+        rates = [int(rates)] * n if np.isscalar(rates) else [int(r) for r in rates]
+        assert len(rates) == n, "one sample rate per clip"
+        fbt = self._f32(fb) if fb is not None else None
+        if fbt is not None:
+            assert tuple(fbt.shape) == (n_fft // 2 + 1, n_mels), "fb must be [n_fft/2+1, n_mels]"
+        blocks, host, host_floats = [], [], 0
+        for w in clips:
+            if isinstance(w, np.ndarray):
+                w = torch.from_numpy(w)
+            if w.dim() == 1:
+                w = w.unsqueeze(0)
+            assert w.dim() == 2, "a clip is [C, L] or [L]"
+            if w.dtype != torch.float32:
+                w = w.float()
+            if w.shape[0] > 2:    # torch's own rounding for surround
+                w = torch.mean(w, dim=0, keepdim=True)
+            if w.device.type == "cpu":
+                w = w.contiguous()
+                host.append(w.reshape(-1))
+                blocks.append((None, host_floats, w.shape[0], w.shape[1], w.shape[1]))
+                host_floats += w.numel()
+                continue
+            if w.device != self.device:
+                w = w.to(self.device)
+            if w.shape[1] > 1 and w.stride(1) != 1 or w.shape[0] == 2 and w.stride(0) < w.shape[1]:
+                w = w.contiguous()
+            blocks.append((w, 0, w.shape[0], w.shape[1], w.stride(0) if w.shape[0] == 2 else w.shape[1]))
+        up = None
+        if host_floats:
+            up = torch.cat(host).to(self.device)       # the batch's host clips in one copy
+            self.frontend_bytes += host_floats * 4
+        ptrs = [(up.data_ptr() + 4 * off) if w is None else w.data_ptr() for w, off, C, L, rs in blocks]
+        live = [q for q, b in zip(ptrs, blocks) if b[3] > 0]
+        base = min(live) if live else 0
+        assert all((q - base) % 4 == 0 for q in live)
+        offsets = [(q - base) // 4 if b[3] > 0 else 0 for q, b in zip(ptrs, blocks)]
+        plan, order, groups, tot = self.frontend_plan([b[2] for b in blocks], [b[3] for b in blocks], rates, common_sr,
+                                                      n_fft, hop, offsets=offsets, row_strides=[b[4] for b in blocks])
+        n_frames, first_frame = plan["n_frames"].copy(), plan["first_frame"].copy()
+        total = tot["n_frames"]
+        out = self.empty((total, n_mels) if frame_major else (total * n_mels,))
+        bad = self.zeros((n,), dtype=torch.int32)
+        if n == 0:
+            return out, n_frames, first_frame, bad
+        table = np.concatenate([plan.view(np.uint8), order.view(np.uint8)])
+        table_dev = torch.from_numpy(table).to(self.device)
+        self.frontend_bytes += table.nbytes
+        plan_ptr, order_ptr = _vp(table_dev.data_ptr()), _vp(table_dev.data_ptr() + plan.nbytes)
+        mono = self.empty((max(tot["mono_floats"], 4),))
+        if pad_value is not None:
+            mono.fill_(pad_value)
+        totals = np.zeros(1, np.dtype(_lib.FRONTEND_TOTALS_FIELDS))
+        for name, v in tot.items():
+            totals[0][name] = v
+        with torch.cuda.device(self.device):
+            for g in range(len(groups)):
+                _lib.check(self.lib.at_mix_resample_ragged_f32(
+                    self.ctx.handle, _vp(base), plan_ptr, order_ptr, _vp(groups.ctypes.data + g * groups.itemsize),
+                    _ptr(mono), self._stream()))
+                self.frontend_calls += 1
+            _lib.check(self.lib.at_logmel_ragged_f32(
+                self.ctx.handle, _ptr(mono), plan_ptr, n, _np_ptr(totals), common_sr, n_fft, hop, n_mels, _ptr(fbt),
+                _ptr(out), _lib.AT_LAYOUT_FRAME_MAJOR if frame_major else _lib.AT_LAYOUT_MEL_MAJOR, 1 if l2norm else 0,
+                _ptr(bad), self._stream()))
+            self.frontend_calls += 1
+        self.frontend_last = {"mono": mono, "plan": plan, "order": order, "groups": groups, "totals": tot}
+        return out, n_frames, first_frame, bad
+
     def flac_decode(self, blobs):
         """FLAC files (bytes each) -> per blob, in order, (float32 [C, L] device tensor, sample_rate), the values
         torchaudio.load returns, or None for a blob that did not index or decode.  One index pass on the host, ONE upload
@@ -334,6 +454,9 @@ class HipBackend(HostHelpers):
         dev = host.to(self.device, non_blocking=True)
         out, clip_status = self._flac_launch(dev, plan)
         decoded = clip_status.cpu().tolist()                 # (waits for the decode, and so for the upload)
+        # the flat buffer and the table of the clips that decoded, in order: what frontend_ragged accepts as `clips`
+        self.flac_flat = (out, [(f[2], f[0]["channels"], f[0]["total_samples"])
+                                for c, f in enumerate(plan["facts"]) if f is not None and decoded[c] == 0])
         res = []
         for c, f in enumerate(plan["facts"]):
             if f is None:

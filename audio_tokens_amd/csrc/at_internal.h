@@ -80,8 +80,17 @@ enum at_ws_slot {
     WS_SILHOUETTE,     // at_silhouette_f32: sorted labels, permutation, segments, offsets, norms, rocprim temp storage
     WS_KNN_IMG,        // at_knn_f32: chunked centroid image (at_prep_chunked_image)
     WS_KNN,            // at_knn_f32 general path: keys of a block of rows (in, out), segment offsets, rocprim temp storage
+    WS_RAGGED_TAPS0,   // at_mix_resample_ragged_f32: the taps of up to four reduced rate pairs (four consecutive slots)
+    WS_RAGGED_TAPS1,
+    WS_RAGGED_TAPS2,
+    WS_RAGGED_TAPS3,
     WS_NSLOTS
 };
+
+// resampler tiling, shared by at_resample_f32, at_mix_resample_ragged_f32 and the plan that sizes the latter's launches
+constexpr int AT_RS_RI = 4;              // accumulators per thread of the tiled kernel
+constexpr int AT_RS_SEG_FLOATS = 8192;   // 32 KiB of LDS per workgroup
+constexpr int AT_RS_COPY_PER_BLOCK = 4096;   // samples per workgroup where there is no filter
 
 // Asynchronous exact calls leave their statistics words (and the events that time their stage-1 kernel) in a
 // ring of slots; slots are folded into the totals when their copy has arrived -- polled, never waited for, unless
@@ -141,6 +150,8 @@ struct at_ctx {
     uint32_t mt_seed;
     int n_cus;             // multiProcessorCount of the device (read once in at_create)
     int rs_orig, rs_new;  // what WS_RESAMPLE_TAPS currently holds
+    int rg_taps[4][2];    // what WS_RAGGED_TAPS0 .. 3 hold (rate pairs; 0 = nothing), replaced round robin
+    int rg_next;
     int64_t filter_rows, filter_listed;  // fp16-split filter: rows swept / rows handed to the fp32 redo
     int filter_slot;                     // the ring slot (or AT_FILTER_RING, the spare) the sweep being queued belongs to
     double filter_ms;                    // summed stage-1 kernel time, over filter_launches launches
@@ -330,10 +341,12 @@ __device__ __forceinline__ long reflect_index(long q, long L) {
     return q;
 }
 
-// logmel_any.hip: every even n_fft other than 512
+// logmel_any.hip: every even n_fft other than 512.  plan_or_null: the ragged form (at_logmel_ragged_f32) -- `wave` is
+// the intermediate buffer, the device plan says where every clip lies, clip_bad receives the per-clip flags,
+// ragged_frames is the plan's total; L and wave_stride are not used.
 int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, int64_t wave_stride, int sample_rate,
                   int n_fft, int hop, int n_mels, const float* fb_user_dev, float* out, int frame_major,
-                  hipStream_t stream);
+                  const at_frontend_clip* plan_or_null, int32_t* clip_bad, int64_t ragged_frames, hipStream_t stream);
 
 // assign.hip: the centroid image of the any-d sweep (tiles of 32 * na rows, features in chunks of 64, |c|^2 of a tile
 // behind its last chunk, +inf for rows >= k); at_chunked_image_tile_floats(d, na) floats per tile.  Used by knn.hip.

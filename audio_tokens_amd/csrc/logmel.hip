@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "at_internal.h"
@@ -59,6 +60,58 @@ struct LogmelParams {
                             // (at_logmel_minmax_f32: SpectrogramGenerator's normalize option without a reduction pass)
 };
 
+// The ragged form (at_logmel_ragged_f32): the clips of an at_frontend_plan_host plan, each with its own length, frames
+// and place in the output.  `wave` is the intermediate buffer, n_blocks counts the blocks of all clips, and L,
+// wave_stride, T and blocks_per_clip are not used.
+struct RaggedLogmelParams : LogmelParams {
+    const at_frontend_clip* plan;
+    int* clip_bad;          // [n_clips]: set where a value stored for the clip is not finite
+};
+
+// One block of fpb frames: whose it is, and that clip's geometry.
+struct BlockOf {
+    long clip;
+    int t0, T;              // first frame of the block, frames of the clip
+    const float* w;         // the clip
+    long L;
+    float* out_mel;         // the clip's [n_mels][T] block / its first [n_mels] row
+    float* out_frames;
+};
+// uniform: blocks_per_clip blocks per clip
+__device__ __forceinline__ BlockOf block_of(const LogmelParams& p, long blk) {
+    BlockOf b;
+    b.clip = blk / p.blocks_per_clip;
+    b.t0 = (int)(blk - b.clip * p.blocks_per_clip) * p.fpb;
+    b.T = p.T;
+    b.w = p.wave + b.clip * p.wave_stride;
+    b.L = p.L;
+    b.out_mel = p.out + (long)b.clip * p.n_mels * p.T;
+    b.out_frames = p.out + (long)b.clip * p.T * p.n_mels;
+    return b;
+}
+// ragged: the clip whose block prefix is the last one <= blk (a clip without frames shares its prefix with the clip
+// behind it and is never found)
+__device__ __forceinline__ BlockOf block_of(const RaggedLogmelParams& p, long blk) {
+    const bool b32 = p.fpb == 32;
+    long lo = 0, hi = p.n_clips;
+    while (hi - lo > 1) {
+        const long mid = (lo + hi) >> 1;
+        if ((b32 ? p.plan[mid].first_block32 : p.plan[mid].first_block16) <= blk) lo = mid;
+        else hi = mid;
+    }
+    const at_frontend_clip& c = p.plan[lo];
+    BlockOf b;
+    b.clip = lo;
+    b.t0 = (int)(blk - (b32 ? c.first_block32 : c.first_block16)) * p.fpb;
+    b.T = c.n_frames;
+    b.w = p.wave + c.mono_offset;
+    b.L = c.out_length;
+    b.out_mel = p.out + c.first_frame * p.n_mels;
+    b.out_frames = b.out_mel;
+    return b;
+}
+__device__ __forceinline__ int not_finite(float v) { return !(__builtin_fabsf(v) < __builtin_inff()); }
+
 // floats as unsigned keys that order the same way (atomicMin / atomicMax on them)
 __device__ __forceinline__ unsigned ordered_key(float v) {
     const unsigned b = __float_as_uint(v);
@@ -92,8 +145,9 @@ __global__ void __launch_bounds__(256) minmax_apply_kernel(float* __restrict__ x
 
 // PF: the next block's samples are prefetched through registers (needs a block of at most PREFETCH_REGS x WG x 4
 // samples); otherwise they are staged at the top of the block.
-template <bool PF>
-__global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
+// RG: the ragged form.
+template <bool PF, bool RG = false>
+__global__ void __launch_bounds__(WG, 2) logmel_kernel(typename std::conditional<RG, RaggedLogmelParams, LogmelParams>::type p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l16 = lane & 15, grp = lane >> 4;
@@ -141,11 +195,10 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
     const int nsamp4 = (nsamp + 3) >> 2;
     f4 pre[PREFETCH_REGS];
     auto prefetch = [&](long blk) {
-        const long clip = blk / p.blocks_per_clip;
-        const int t0 = (int)(blk - clip * p.blocks_per_clip) * p.fpb;
-        const float* w = p.wave + clip * p.wave_stride;
-        const long s0 = (long)t0 * p.hop - NFFT / 2;
-        const bool fast = s0 >= 0 && s0 + 4L * nsamp4 <= p.L && ((reinterpret_cast<uintptr_t>(w + s0) & 15) == 0);
+        const BlockOf at = block_of(p, blk);
+        const float* w = at.w;
+        const long s0 = (long)at.t0 * p.hop - NFFT / 2;
+        const bool fast = s0 >= 0 && s0 + 4L * nsamp4 <= at.L && ((reinterpret_cast<uintptr_t>(w + s0) & 15) == 0);
         if (fast) {
             const f4* src = reinterpret_cast<const f4*>(w + s0);
 #pragma unroll
@@ -160,7 +213,7 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
                 if (i4 < nsamp4) {
 #pragma unroll
                     for (int e = 0; e < 4; e++) {
-                        pre[j][e] = w[reflect_index(s0 + 4 * i4 + e, p.L)];
+                        pre[j][e] = w[reflect_index(s0 + 4 * i4 + e, at.L)];
                     }
                 }
             }
@@ -169,8 +222,9 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
     if constexpr (PF)
         if ((long)blockIdx.x < p.n_blocks) prefetch(blockIdx.x);
     for (long blk = blockIdx.x; blk < p.n_blocks; blk += gridDim.x) {
-        const long clip = blk / p.blocks_per_clip;
-        const int t0 = (int)(blk - clip * p.blocks_per_clip) * p.fpb;
+        const BlockOf at = block_of(p, blk);
+        const long clip = at.clip;
+        const int t0 = at.t0;
         if constexpr (PF) {
 #pragma unroll
             for (int j = 0; j < PREFETCH_REGS; j++) {
@@ -178,9 +232,9 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
                 if (i4 < nsamp4) *reinterpret_cast<f4*>(samp + 4 * i4) = pre[j];
             }
         } else {
-            const float* w = p.wave + clip * p.wave_stride;
+            const float* w = at.w;
             const long s0 = (long)t0 * p.hop - NFFT / 2;
-            for (int i = tid; i < nsamp; i += WG) samp[i] = w[reflect_index(s0 + i, p.L)];
+            for (int i = tid; i < nsamp; i += WG) samp[i] = w[reflect_index(s0 + i, at.L)];
         }
         __syncthreads();  // samples in place; the previous block's staged output has been stored by everybody
         if constexpr (PF)
@@ -214,7 +268,8 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
         }
         __syncthreads();
 
-        const int nf = min(p.fpb, p.T - t0);  // frames of this block that exist
+        const int nf = min(p.fpb, at.T - t0);  // frames of this block that exist
+        int flagged = 0;                      // (ragged) a value stored by this lane is not finite
         if (p.minmax) {   // the clip's extremes, from the staged block: one pair of atomics per workgroup and block
             float lo = __builtin_inff(), hi = -__builtin_inff();
             int nan = 0;
@@ -252,7 +307,7 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
                 }
                 __syncthreads();
             }
-            float* dst = p.out + ((long)clip * p.T + t0) * p.n_mels;
+            float* dst = at.out_frames + (long)t0 * p.n_mels;
             if ((p.n_mels & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {   // 16 bytes per lane
                 const int mq = p.n_mels >> 2, total4 = nf * mq;
                 for (int e4 = tid; e4 < total4; e4 += WG) {
@@ -264,6 +319,7 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
 #pragma unroll
                         for (int e = 0; e < 4; e++) v[e] = l2n::divide(v[e], dn);
                     }
+                    if constexpr (RG) flagged |= not_finite(v[0]) | not_finite(v[1]) | not_finite(v[2]) | not_finite(v[3]);
                     reinterpret_cast<f4*>(dst)[e4] = v;
                 }
             } else {
@@ -272,17 +328,24 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams p) {
                     const int f = e / p.n_mels, m = e - f * p.n_mels;
                     float v = ostage[f * opitch + m];
                     if (p.fuse_l2norm) v = l2n::divide(v, den[f]);
+                    if constexpr (RG) flagged |= not_finite(v);
                     dst[e] = v;
                 }
             }
         } else {
-            float* dst = p.out + (long)clip * p.n_mels * p.T + t0;
+            float* dst = at.out_mel + t0;
             const int total = p.n_mels * p.fpb;
             for (int e = tid; e < total; e += WG) {
                 const int m = e / p.fpb, f = e - m * p.fpb;
-                if (f < nf) dst[(long)m * p.T + f] = ostage[f * opitch + m];
+                if (f < nf) {
+                    const float v = ostage[f * opitch + m];
+                    if constexpr (RG) flagged |= not_finite(v);
+                    dst[(long)m * at.T + f] = v;
+                }
             }
         }
+        if constexpr (RG)
+            if (flagged) p.clip_bad[clip] = 1;   // (every writer stores the same value)
         // (no barrier here: the next block's samples go to `samp`, which nobody reads any more, and its
         // barrier above comes before anybody writes the staged output again)
     }
@@ -370,39 +433,14 @@ int at_logmel_resident(at_ctx* ctx, int slot, at_logmel_tables* rec, const at_lo
     return AT_OK;
 }
 
-static int logmel_impl(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L,
-                       int64_t wave_stride, int sample_rate, int n_fft, int hop, int n_mels,
-                       const float* fb_or_null, float* out, int layout, int fuse_l2norm,
-                       unsigned* minmax, hipStream_t stream) {
-    AT_REQUIRE(ctx, "at_logmel_f32: ctx is null");
-    AT_REQUIRE(n_fft >= 64 && n_fft <= 4096, "at_logmel_f32: n_fft=%d out of range (an even size from 64 to 4096)", n_fft);
-    AT_REQUIRE((n_fft & 1) == 0,
-               "at_logmel_f32: odd n_fft=%d is not supported (torch counts 1 + (L - 1) / hop frames for odd sizes, "
-               "at_num_frames has no n_fft argument; use an even size from 64 to 4096)", n_fft);
-    AT_REQUIRE(hop >= 1 && hop <= n_fft, "at_logmel_f32: hop=%d out of range [1, %d]", hop, n_fft);
-    AT_REQUIRE(n_mels >= 1 && n_mels <= 1024, "at_logmel_f32: n_mels=%d out of range", n_mels);
-    AT_REQUIRE(n_clips >= 0 && n_clips <= 65535 * 1024L, "at_logmel_f32: n_clips out of range");
-    AT_REQUIRE(L > n_fft / 2, "at_logmel_f32: clip length %lld must exceed n_fft/2 (reflect padding)", (long long)L);
-    AT_REQUIRE(wave_stride >= L, "at_logmel_f32: wave_stride < L");
-    AT_REQUIRE(layout == AT_LAYOUT_MEL_MAJOR || layout == AT_LAYOUT_FRAME_MAJOR, "at_logmel_f32: bad layout");
-    AT_REQUIRE(!fuse_l2norm || layout == AT_LAYOUT_FRAME_MAJOR, "at_logmel_f32: fuse_l2norm needs the frame-major layout");
-    if (n_clips == 0) return AT_OK;
-    AT_REQUIRE(wave && out, "at_logmel_f32: null pointer");
-    AT_HIP(hipSetDevice(ctx->device));
-    if (n_fft != NFFT) {   // the general form (logmel_any.hip); unit rows by the stand-alone kernel behind it
-        AT_REQUIRE(at_num_frames(L, hop) < (1LL << 31), "at_logmel_f32: too many frames per clip");
-        int rc = at_logmel_any(ctx, wave, n_clips, L, wave_stride, sample_rate, n_fft, hop, n_mels, fb_or_null, out,
-                               layout == AT_LAYOUT_FRAME_MAJOR, stream);
-        if (rc) return rc;
-        if (fuse_l2norm) {
-            int* bad = at_row_flag(ctx, stream);
-            if (!bad) return AT_E_NOMEM;
-            return at_l2norm_rows_flagged(ctx, out, n_clips * at_num_frames(L, hop), n_mels, out, bad, stream);
-        }
-        return AT_OK;
-    }
-
-    LogmelParams p;
+// What the uniform and the ragged launch of the tuned kernel share: argument checks are the caller's; this fills the
+// tables, the frames per block, the LDS size and which of the two kernels (prefetch or not) applies.
+struct Setup512 {
+    size_t lds;
+    bool pf, fuse_here;
+};
+static int setup_512(at_ctx* ctx, int sample_rate, int hop, int n_mels, const float* fb_or_null, int fuse_l2norm,
+                     hipStream_t stream, LogmelParams& p, Setup512& su) {
     const at_logmel_tables key{sample_rate, NFFT, n_mels, hop, /* form */ 0};
     const lmt::BlobLayout lay = lmt::blob_layout(TAB_FLOATS, n_mels);
     // (capacity: the worst case, every bin of every filter and its quad padding)
@@ -413,41 +451,139 @@ static int logmel_impl(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t 
     p.fb_len = p.fb_start + n_mels; p.fb_off = p.fb_start + 2 * n_mels;
     p.fb_wts = p.tabs + lay.wts;
     p.fb_nw = ctx->lm_fb.nw; p.fb_quads = ctx->lm_fb.quads;
-    const int64_t T = at_num_frames(L, hop);
-    AT_REQUIRE(T < (1LL << 31), "at_logmel_f32: too many frames per clip");
-    p.wave = wave; p.n_clips = n_clips; p.L = L; p.wave_stride = wave_stride;
-    p.hop = hop; p.T = (int)T; p.n_mels = n_mels;
+    p.hop = hop; p.n_mels = n_mels;
     // unit rows are fused for 8 <= n_mels <= 128 (numpy's one-level pairwise sum, eight lanes per frame);
     // other widths get the standalone kernel behind this one, in place
-    const bool fuse_here = fuse_l2norm && n_mels >= 8 && n_mels <= 128;
-    p.out = out; p.frame_major = layout == AT_LAYOUT_FRAME_MAJOR; p.fuse_l2norm = fuse_here;
+    su.fuse_here = fuse_l2norm && n_mels >= 8 && n_mels <= 128;
+    p.fuse_l2norm = su.fuse_here;
     p.bad = fuse_l2norm ? at_row_flag(ctx, stream) : nullptr;
     if (fuse_l2norm && !p.bad) return AT_E_NOMEM;
-    p.minmax = minmax;
     // the banded filterbank rides in LDS too unless a dense user filterbank makes it too big
     const size_t fb_ints = lmt::table_ints(n_mels) + p.fb_nw;
     p.fb_lds = fb_ints * 4 <= 14 * 1024;
     // 32 frames per workgroup when two workgroups of that size still share a CU's 160 KiB of LDS
     // (the kernel is latency-bound: one workgroup per CU runs at half the rate), else 16
-    size_t lds = 0;
+    su.lds = 0;
     for (p.fpb = 32; p.fpb >= 16; p.fpb -= 16) {
-        lds = lds_bytes(p.fpb, hop, n_mels, p.fb_lds ? fb_ints : 0);
-        if (lds <= LDS_TWO_PER_CU || p.fpb == 16) break;
+        su.lds = lds_bytes(p.fpb, hop, n_mels, p.fb_lds ? fb_ints : 0);
+        if (su.lds <= LDS_TWO_PER_CU || p.fpb == 16) break;
     }
-    AT_REQUIRE(lds <= 160 * 1024, "at_logmel_f32: n_mels=%d needs %zu bytes of LDS", n_mels, lds);
-    const bool pf = ((p.fpb - 1) * hop + NFFT + 3) / 4 <= PREFETCH_REGS * WG;   // the block's samples fit the prefetch registers
-    AT_RAISE_LDS(ctx, logmel_kernel<true>, lds);
-    AT_RAISE_LDS(ctx, logmel_kernel<false>, lds);
+    AT_REQUIRE(su.lds <= 160 * 1024, "at_logmel_f32: n_mels=%d needs %zu bytes of LDS", n_mels, su.lds);
+    su.pf = ((p.fpb - 1) * hop + NFFT + 3) / 4 <= PREFETCH_REGS * WG;   // the block's samples fit the prefetch registers
+    return AT_OK;
+}
+
+static int check_logmel_args(const char* who, at_ctx* ctx, int n_fft, int hop, int n_mels, int layout, int fuse_l2norm) {
+    AT_REQUIRE(ctx, "%s: ctx is null", who);
+    AT_REQUIRE(n_fft >= 64 && n_fft <= 4096, "%s: n_fft=%d out of range (an even size from 64 to 4096)", who, n_fft);
+    AT_REQUIRE((n_fft & 1) == 0,
+               "%s: odd n_fft=%d is not supported (torch counts 1 + (L - 1) / hop frames for odd sizes, "
+               "at_num_frames has no n_fft argument; use an even size from 64 to 4096)", who, n_fft);
+    AT_REQUIRE(hop >= 1 && hop <= n_fft, "%s: hop=%d out of range [1, %d]", who, hop, n_fft);
+    AT_REQUIRE(n_mels >= 1 && n_mels <= 1024, "%s: n_mels=%d out of range", who, n_mels);
+    AT_REQUIRE(layout == AT_LAYOUT_MEL_MAJOR || layout == AT_LAYOUT_FRAME_MAJOR, "%s: bad layout", who);
+    AT_REQUIRE(!fuse_l2norm || layout == AT_LAYOUT_FRAME_MAJOR, "%s: fuse_l2norm needs the frame-major layout", who);
+    return AT_OK;
+}
+
+static int logmel_impl(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L,
+                       int64_t wave_stride, int sample_rate, int n_fft, int hop, int n_mels,
+                       const float* fb_or_null, float* out, int layout, int fuse_l2norm,
+                       unsigned* minmax, hipStream_t stream) {
+    int rc = check_logmel_args("at_logmel_f32", ctx, n_fft, hop, n_mels, layout, fuse_l2norm);
+    if (rc) return rc;
+    AT_REQUIRE(n_clips >= 0 && n_clips <= 65535 * 1024L, "at_logmel_f32: n_clips out of range");
+    AT_REQUIRE(L > n_fft / 2, "at_logmel_f32: clip length %lld must exceed n_fft/2 (reflect padding)", (long long)L);
+    AT_REQUIRE(wave_stride >= L, "at_logmel_f32: wave_stride < L");
+    if (n_clips == 0) return AT_OK;
+    AT_REQUIRE(wave && out, "at_logmel_f32: null pointer");
+    AT_HIP(hipSetDevice(ctx->device));
+    if (n_fft != NFFT) {   // the general form (logmel_any.hip); unit rows by the stand-alone kernel behind it
+        AT_REQUIRE(at_num_frames(L, hop) < (1LL << 31), "at_logmel_f32: too many frames per clip");
+        rc = at_logmel_any(ctx, wave, n_clips, L, wave_stride, sample_rate, n_fft, hop, n_mels, fb_or_null, out,
+                           layout == AT_LAYOUT_FRAME_MAJOR, nullptr, nullptr, 0, stream);
+        if (rc) return rc;
+        if (fuse_l2norm) {
+            int* bad = at_row_flag(ctx, stream);
+            if (!bad) return AT_E_NOMEM;
+            return at_l2norm_rows_flagged(ctx, out, n_clips * at_num_frames(L, hop), n_mels, out, bad, stream);
+        }
+        return AT_OK;
+    }
+
+    LogmelParams p;
+    Setup512 su;
+    rc = setup_512(ctx, sample_rate, hop, n_mels, fb_or_null, fuse_l2norm, stream, p, su);
+    if (rc) return rc;
+    const int64_t T = at_num_frames(L, hop);
+    AT_REQUIRE(T < (1LL << 31), "at_logmel_f32: too many frames per clip");
+    p.wave = wave; p.n_clips = n_clips; p.L = L; p.wave_stride = wave_stride;
+    p.T = (int)T;
+    p.out = out; p.frame_major = layout == AT_LAYOUT_FRAME_MAJOR;
+    p.minmax = minmax;
+    AT_RAISE_LDS(ctx, logmel_kernel<true>, su.lds);
+    AT_RAISE_LDS(ctx, logmel_kernel<false>, su.lds);
     p.blocks_per_clip = (int)((T + p.fpb - 1) / p.fpb);
     p.n_blocks = (long)p.blocks_per_clip * n_clips;
     // persistent workgroups: two per CU (what the LDS footprint allows), each walking a strided share
     // of the blocks with its window / twiddle tables in registers
     long grid = 2L * ctx->n_cus;
     if (grid > p.n_blocks) grid = p.n_blocks;
-    if (pf) AT_LAUNCH(logmel_kernel<true>, dim3((unsigned)grid), dim3(WG), lds, stream, p);
-    else AT_LAUNCH(logmel_kernel<false>, dim3((unsigned)grid), dim3(WG), lds, stream, p);
-    if (fuse_l2norm && !fuse_here) return at_l2norm_rows_flagged(ctx, out, n_clips * T, n_mels, out, p.bad, stream);
+    if (su.pf) AT_LAUNCH(logmel_kernel<true>, dim3((unsigned)grid), dim3(WG), su.lds, stream, p);
+    else AT_LAUNCH(logmel_kernel<false>, dim3((unsigned)grid), dim3(WG), su.lds, stream, p);
+    if (fuse_l2norm && !su.fuse_here) return at_l2norm_rows_flagged(ctx, out, n_clips * T, n_mels, out, p.bad, stream);
     return AT_OK;
+}
+
+// at_logmel_f32 for the clips of an at_frontend_plan_host plan, one launch (include/audio_tokens_amd.h).  The same
+// kernels over the same tables as the uniform call; only where a block or frame finds its clip differs.
+extern "C" int at_logmel_ragged_f32(at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev, int64_t n_clips,
+                                    const at_frontend_totals* totals, int sample_rate, int n_fft, int hop, int n_mels,
+                                    const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad,
+                                    void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = check_logmel_args("at_logmel_ragged_f32", ctx, n_fft, hop, n_mels, layout, fuse_l2norm);
+    if (rc) return rc;
+    AT_REQUIRE(n_clips >= 0 && n_clips < (1LL << 31), "at_logmel_ragged_f32: n_clips out of range");
+    if (n_clips == 0) return AT_OK;
+    AT_REQUIRE(totals && plan_dev && bad, "at_logmel_ragged_f32: null pointer");
+    AT_REQUIRE(totals->n_frames >= 0 && totals->n_blocks16 >= 0 && totals->n_blocks32 >= 0 &&
+                   totals->n_blocks32 <= totals->n_blocks16 && totals->n_blocks16 <= totals->n_frames,
+               "at_logmel_ragged_f32: bad totals");
+    AT_HIP(hipSetDevice(ctx->device));
+    AT_HIP(hipMemsetAsync(bad, 0, (size_t)n_clips * sizeof(int32_t), stream));
+    if (totals->n_frames == 0) return AT_OK;   // every clip too short
+    AT_REQUIRE(mono && out, "at_logmel_ragged_f32: null pointer");
+    if (n_fft != NFFT) {
+        rc = at_logmel_any(ctx, mono, n_clips, 0, 0, sample_rate, n_fft, hop, n_mels, fb_or_null, out,
+                           layout == AT_LAYOUT_FRAME_MAJOR, plan_dev, bad, totals->n_frames, stream);
+        if (rc) return rc;
+    } else {
+        RaggedLogmelParams p;
+        Setup512 su;
+        rc = setup_512(ctx, sample_rate, hop, n_mels, fb_or_null, fuse_l2norm, stream, p, su);
+        if (rc) return rc;
+        p.wave = mono; p.n_clips = n_clips; p.L = 0; p.wave_stride = 0; p.T = 0; p.blocks_per_clip = 0;
+        p.out = out; p.frame_major = layout == AT_LAYOUT_FRAME_MAJOR;
+        p.minmax = nullptr;
+        p.plan = plan_dev; p.clip_bad = bad;
+        p.n_blocks = (long)(p.fpb == 32 ? totals->n_blocks32 : totals->n_blocks16);
+        AT_RAISE_LDS(ctx, (logmel_kernel<true, true>), su.lds);
+        AT_RAISE_LDS(ctx, (logmel_kernel<false, true>), su.lds);
+        long grid = 2L * ctx->n_cus;
+        if (grid > p.n_blocks) grid = p.n_blocks;
+        if (su.pf) AT_LAUNCH((logmel_kernel<true, true>), dim3((unsigned)grid), dim3(WG), su.lds, stream, p);
+        else AT_LAUNCH((logmel_kernel<false, true>), dim3((unsigned)grid), dim3(WG), su.lds, stream, p);
+        if (!fuse_l2norm || su.fuse_here) return AT_OK;
+    }
+    // unit rows by the stand-alone kernel, in place.  The clips' flags, set from the dB values, hold for the unit rows:
+    // a NaN or Inf in a row makes the row NaN, and a finite row stays finite.
+    if (fuse_l2norm) {
+        int* flag = at_row_flag(ctx, stream);
+        if (!flag) return AT_E_NOMEM;
+        rc = at_l2norm_rows_flagged(ctx, out, totals->n_frames, n_mels, out, flag, stream);
+    }
+    return rc;
 }
 
 extern "C" int at_logmel_f32(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L,

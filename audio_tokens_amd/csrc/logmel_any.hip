@@ -40,7 +40,48 @@ struct AnyParams {
     const float* fb_wts;
     float* out;
     int frame_major;
+    // the ragged form (at_logmel_ragged_f32): n_frames counts the frames of all clips; L, wave_stride and T are not used
+    const at_frontend_clip* plan;
+    int* clip_bad;           // [n_clips]: set where a value stored for the clip is not finite
 };
+
+// One frame: whose it is, and that clip's geometry.
+struct FrameOf {
+    long clip;
+    int t, T;               // frame within the clip, frames of the clip
+    const float* w;         // the clip
+    long L;
+    long mel_base;          // offset of the clip's [n_mels][T] block in the mel-major output
+};
+template <bool RG>
+__device__ __forceinline__ FrameOf frame_of(const AnyParams& p, long g) {
+    FrameOf f;
+    if constexpr (RG) {
+        // the clip whose first frame is the last one <= g (a clip without frames shares its prefix with the clip
+        // behind it and is never found)
+        long lo = 0, hi = p.n_clips;
+        while (hi - lo > 1) {
+            const long mid = (lo + hi) >> 1;
+            if (p.plan[mid].first_frame <= g) lo = mid;
+            else hi = mid;
+        }
+        const at_frontend_clip& c = p.plan[lo];
+        f.clip = lo;
+        f.t = (int)(g - c.first_frame);
+        f.T = c.n_frames;
+        f.w = p.wave + c.mono_offset;
+        f.L = c.out_length;
+        f.mel_base = c.first_frame * p.n_mels;
+    } else {
+        f.clip = g / p.T;
+        f.t = (int)(g - f.clip * p.T);
+        f.T = p.T;
+        f.w = p.wave + f.clip * p.wave_stride;
+        f.L = p.L;
+        f.mel_base = f.clip * p.n_mels * p.T;
+    }
+    return f;
+}
 
 // One Stockham pass of radix R over M points held by one wavefront: butterfly j (of M/R) takes the inputs
 // j + t*M/R, multiplies input t by W_(NS*R)^(k*t) with k = j mod NS (NS = product of the radices before this pass),
@@ -107,9 +148,9 @@ struct FrameSrc {
     const float* win;   // n_fft window values
     long s0, L;
     bool inner;         // no reflection anywhere in this frame
-    __device__ __forceinline__ FrameSrc(const AnyParams& p, long clip, int t, const float* win_)
-        : w(p.wave + clip * p.wave_stride), win(win_), s0((long)t * p.hop - p.n_fft / 2), L(p.L) {
-        inner = s0 >= 0 && s0 + p.n_fft <= p.L;
+    __device__ __forceinline__ FrameSrc(const AnyParams& p, const FrameOf& f, const float* win_)
+        : w(f.w), win(win_), s0((long)f.t * p.hop - p.n_fft / 2), L(f.L) {
+        inner = s0 >= 0 && s0 + p.n_fft <= L;
     }
     __device__ __forceinline__ cx operator()(int m) const {
         float v[2];
@@ -133,20 +174,25 @@ __device__ __forceinline__ void untangle_frame(int lane, int M, const float* z, 
 }
 
 // banded mel dot products, 10 log10, store in either layout
-__device__ __forceinline__ void mel_db_store(int lane, const AnyParams& p, const float* pw, long g, long clip, int t) {
+template <bool RG>
+__device__ __forceinline__ void mel_db_store(int lane, const AnyParams& p, const float* pw, long g, const FrameOf& f) {
+    int flagged = 0;
     for (int m = lane; m < p.n_mels; m += 64) {
         const float* wt = p.fb_wts + p.fb_off[m];
         const int st = p.fb_start[m], ln = p.fb_len[m];
         float acc = 0.0f;
         for (int q = 0; q < ln; q++) acc = __builtin_fmaf(pw[st + q], wt[q], acc);
         const float db = !(acc <= 1e-10f) ? 10.0f * log10f(acc) : -100.0f;   // (a NaN power stays NaN, as torch.clamp leaves it)
+        if constexpr (RG) flagged |= !(__builtin_fabsf(db) < __builtin_inff());
         if (p.frame_major) p.out[g * p.n_mels + m] = db;
-        else p.out[(clip * p.n_mels + m) * p.T + t] = db;
+        else p.out[f.mel_base + (long)m * f.T + f.t] = db;
     }
+    if constexpr (RG)
+        if (flagged) p.clip_bad[f.clip] = 1;   // (every writer stores the same value)
     __builtin_amdgcn_wave_barrier();   // the next frame overwrites the buffers
 }
 
-template <int LOG2M>
+template <int LOG2M, bool RG = false>
 __global__ void __launch_bounds__(WG) logmel_any_kernel(AnyParams p) {
     constexpr int M = 1 << LOG2M, N = 2 * M;
     extern __shared__ __attribute__((aligned(16))) float sm[];   // W_M (2M) | W_N (2M) | window (N) | per wave: z (N) + power (M + 4)
@@ -163,12 +209,11 @@ __global__ void __launch_bounds__(WG) logmel_any_kernel(AnyParams p) {
     float* z = sm + 6 * M + (size_t)wave * (N + M + 4);
     float* pw = z + N;
     for (long g = (long)blockIdx.x * (WG / 64) + wave; g < p.n_frames; g += (long)gridDim.x * (WG / 64)) {
-        const long clip = g / p.T;
-        const int t = (int)(g - clip * p.T);
-        const FrameSrc load(p, clip, t, win);
+        const FrameOf f = frame_of<RG>(p, g);
+        const FrameSrc load(p, f, win);
         fft_passes<M, 1, true>(lane, z, tw, load);
         untangle_frame(lane, M, z, twn, pw);
-        mel_db_store(lane, p, pw, g, clip, t);
+        mel_db_store<RG>(lane, p, pw, g, f);
     }
 }
 
@@ -188,9 +233,8 @@ struct MixedParams {
     const float* bhat;           // form 2: P x transform of the chirp filter, / P
 };
 
-// (__launch_bounds__(WG) is the upper bound: the launch uses 64 .. 256 threads, launch_mixed)
-template <bool BLUE>
-__global__ void __launch_bounds__(WG) logmel_mixed_kernel(MixedParams p) {
+template <bool BLUE, bool RG>
+__device__ __forceinline__ void mixed_body(const MixedParams& p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];   // W_P (2P) | W_N (2M) | per wave: two buffers of 2P
     const int M = p.a.n_fft / 2, P = p.P;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -201,23 +245,37 @@ __global__ void __launch_bounds__(WG) logmel_mixed_kernel(MixedParams p) {
     __syncthreads();
     float* buf = sm + 2 * P + 2 * M + (size_t)wave * 4 * P;
     for (long g = (long)blockIdx.x * nw + wave; g < p.a.n_frames; g += (long)gridDim.x * nw) {
-        const long clip = g / p.a.T;
-        const int t = (int)(g - clip * p.a.T);
-        const FrameSrc src(p.a, clip, t, p.a.win);
+        const FrameOf f = frame_of<RG>(p.a, g);
+        const FrameSrc src(p.a, f, p.a.win);
         float* cur = buf;           // after a transform: its result; the first pass of a transform writes `oth`
         float* oth = buf + 2 * P;
         const Lanes me{lane, lane + 1};
         frame_transform<BLUE>(me, M, P, p.npass, p.packed, tw, p.chirp, p.bhat, src, cur, oth, WaveBarrier{});
         untangle_lanes(me, M, cur, twn, oth, WaveBarrier{});
-        mel_db_store(lane, p.a, oth, g, clip, t);
+        mel_db_store<RG>(lane, p.a, oth, g, f);
     }
+}
+
+// (__launch_bounds__(WG) is the upper bound: the launch uses 64 .. 256 threads, launch_mixed)
+template <bool BLUE>
+__global__ void __launch_bounds__(WG) logmel_mixed_kernel(MixedParams p) {
+    mixed_body<BLUE, false>(p);
+}
+// the ragged form of the two
+template <bool BLUE>
+__global__ void __launch_bounds__(WG) logmel_ragged_mx_kernel(MixedParams p) {
+    mixed_body<BLUE, true>(p);
 }
 
 template <int LOG2M>
 int launch_any(at_ctx* ctx, const AnyParams& p, hipStream_t stream) {
+    auto kernel = p.plan ? logmel_any_kernel<LOG2M, true> : logmel_any_kernel<LOG2M, false>;
     constexpr int M = 1 << LOG2M, N = 2 * M;
     const size_t lds = ((size_t)6 * M + (size_t)(WG / 64) * (N + M + 4)) * sizeof(float);
-    AT_RAISE_LDS(ctx, logmel_any_kernel<LOG2M>, lds);
+    {
+        const int rc = at_raise_lds(ctx, reinterpret_cast<const void*>(kernel), lds);
+        if (rc) return rc;
+    }
     // persistent: as many workgroups as fit the LDS of the chip (at most eight per CU), each wave walking frames
     long per_cu = (long)(160 * 1024 / lds);
     if (per_cu < 1) per_cu = 1;
@@ -225,7 +283,7 @@ int launch_any(at_ctx* ctx, const AnyParams& p, hipStream_t stream) {
     long grid = per_cu * ctx->n_cus;
     const long need = (p.n_frames + WG / 64 - 1) / (WG / 64);
     if (grid > need) grid = need;
-    AT_LAUNCH(logmel_any_kernel<LOG2M>, dim3((unsigned)grid), dim3(WG), lds, stream, p);
+    AT_LAUNCH(kernel, dim3((unsigned)grid), dim3(WG), lds, stream, p);
     return AT_OK;
 }
 
@@ -238,13 +296,17 @@ int launch_mixed(at_ctx* ctx, const MixedParams& p, hipStream_t stream) {
     while (nw > 1 && tabs + nw * per_wave > 160 * 1024) nw--;
     const size_t lds = tabs + nw * per_wave;
     if (lds > 160 * 1024) return at_fail(AT_E_INVALID, "at_logmel_f32: n_fft=%d needs %zu bytes of LDS", p.a.n_fft, lds);
-    AT_RAISE_LDS(ctx, logmel_mixed_kernel<BLUE>, lds);
+    auto kernel = p.a.plan ? logmel_ragged_mx_kernel<BLUE> : logmel_mixed_kernel<BLUE>;
+    {
+        const int rc = at_raise_lds(ctx, reinterpret_cast<const void*>(kernel), lds);
+        if (rc) return rc;
+    }
     long per_cu = (long)(160 * 1024 / lds);   // persistent, as the power-of-two kernel
     if (per_cu > 8) per_cu = 8;
     long grid = per_cu * ctx->n_cus;
     const long need = (p.a.n_frames + nw - 1) / nw;
     if (grid > need) grid = need;
-    AT_LAUNCH(logmel_mixed_kernel<BLUE>, dim3((unsigned)grid), dim3(64 * nw), lds, stream, p);
+    AT_LAUNCH(kernel, dim3((unsigned)grid), dim3(64 * nw), lds, stream, p);
     return AT_OK;
 }
 
@@ -254,7 +316,7 @@ int launch_mixed(at_ctx* ctx, const MixedParams& p, hipStream_t stream) {
 // transform | start, len, off | band weights.  Form 0 = a power of two (logmel_any_kernel), else lmx::Plan::form.
 int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, int64_t wave_stride, int sample_rate,
                   int n_fft, int hop, int n_mels, const float* fb_user_dev, float* out, int frame_major,
-                  hipStream_t stream) {
+                  const at_frontend_clip* plan_or_null, int32_t* clip_bad, int64_t ragged_frames, hipStream_t stream) {
     const int N = n_fft, M = N / 2, NBIN = M + 1;
     int log2m = 0;
     while ((1 << log2m) < M) log2m++;
@@ -284,9 +346,10 @@ int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, in
     AnyParams p;
     p.wave = wave; p.n_clips = n_clips; p.L = L; p.wave_stride = wave_stride;
     p.n_fft = N; p.log2m = log2m; p.hop = hop; p.n_mels = n_mels;
-    const int64_t T = at_num_frames(L, hop);
+    const int64_t T = plan_or_null ? 0 : at_num_frames(L, hop);
     p.T = (int)T;
-    p.n_frames = n_clips * T;
+    p.n_frames = plan_or_null ? ragged_frames : n_clips * T;
+    p.plan = plan_or_null; p.clip_bad = clip_bad;
     p.win = f; p.twm = f + N; p.twn = f + N + 2 * M;
     p.fb_start = reinterpret_cast<const int*>(f + lay.ints);
     p.fb_len = p.fb_start + n_mels; p.fb_off = p.fb_start + 2 * n_mels;

@@ -111,6 +111,22 @@ class LogMelSpectrogram:
                         self.n_mels, fb=self.fb)
         return out.reshape(*lead, self.n_mels, out.shape[-1])
 
+    def batch(self, waveforms, sample_rates=None):
+        """Clips of any length, channel count and sample rate -> a list of [n_mels, T_i] dB spectrograms in input order,
+        views of one flat device tensor; None where a clip is too short for the reflect padding (its length at
+        self.sample_rate <= n_fft / 2).  waveforms: [C_i, L_i] or [L_i] tensors; sample_rates: one per clip (default:
+        all at self.sample_rate).  Stereo is mixed to mono and other rates are resampled to self.sample_rate, with the
+        bits of torch.mean and Resample per clip, in one launch per rate pair present and one log-mel launch
+        (HipBackend.frontend_ragged).  self.last_bad: device int32 per clip, non-zero where its spectrogram holds a NaN
+        or Inf."""
+        be = self.backend
+        rates = self.sample_rate if sample_rates is None else sample_rates
+        out, T, first, self.last_bad = be.frontend_ragged(waveforms, rates, self.sample_rate, self.n_fft, self.hop_length,
+                                                          self.n_mels, fb=self.fb)
+        m = self.n_mels
+        return [None if T[i] == 0 else out[m * int(first[i]): m * (int(first[i]) + int(T[i]))].view(m, int(T[i]))
+                for i in range(len(T))]
+
     def frames(self, waveform, l2norm=False):
         """[n_clips, L] -> frame-major [n_clips*T, n_mels] (optionally row-normalised): the matrix
         ClusterCreator / SpecTokenizer build from the .npy files, without the round trip."""

@@ -3,10 +3,11 @@ danavery/audio-tokens) on the MI355X log-mel kernel.
 
 Same constructor, methods, outputs (spectrograms/{train,validation}/<ytid>.npy, float32
 [n_mels, T]) and skip-and-continue error behaviour.  Differences in HOW, not WHAT:
-  * clips of one batch are decoded on the host, stacked by length and pushed through ONE fused
-    STFT -> mel -> dB launch per length (the reference launches a dozen kernels per clip);
-  * the whole batch comes back in one device->host copy before the per-file np.save.
-  * clips at another sample rate go through the device polyphase resampler (ops.Resample).
+  * the clips of one batch -- any length, mono or stereo, any rate -- go through the ragged front end: one mono-mix /
+    resampler launch per rate pair present and ONE fused STFT -> mel -> dB launch (the reference launches a dozen
+    kernels per clip); the whole batch comes back in one device->host copy before the per-file np.save, the per-clip
+    NaN / Inf flags in another (SpectrogramGenerator.ragged; DESIGN.md section 6d);
+  * with normalize=True, or ragged=False: one resampler call per clip (ops.Resample) and one launch per clip length.
 .flac files are decoded on the device (ops.load_flac / load_flac_batch: all of a batch in one call) and stay there
 through the mono mix and the resampler.  Other audio is decoded on the CPU: torchaudio.load if torchaudio is
 importable, otherwise PCM/float .wav through the standard library and raw float32 .npy waveforms (used by the
@@ -77,6 +78,11 @@ def _load_audio(path: Path):
 
 
 class SpectrogramGenerator:
+    # A/B switch: True = batches go through the ragged front end (one launch per rate pair present, one log-mel launch,
+    # two device->host copies, whatever the clip lengths); False = one resampler call per clip and one log-mel launch
+    # per distinct length.  Both settings write the same files.  (normalize=True batches always take the second route.)
+    ragged = True
+
     def __init__(self, config):
         self.config = config
         self.logger = logging.getLogger(__name__)
@@ -123,6 +129,8 @@ class SpectrogramGenerator:
         be = self.spec_transformer.backend
         flacs = [p for _, p in found if p and p.suffix.lower() == ".flac"]
         decoded = dict(zip(flacs, zip(load_flac_batch(flacs, backend=be), be.flac_status))) if flacs else {}
+        if self.ragged and not self.config.normalize:
+            return self._populate_specs_ragged(found, decoded)
         waves, names = [], []
         for i, audio_file_path in found:
             if not audio_file_path:
@@ -172,6 +180,47 @@ class SpectrogramGenerator:
             specs.append({"filename": os.path.basename(names[j][1]), "spec": specs_by_j[j]})
         return specs
 
+    def _populate_specs_ragged(self, found, decoded):
+        """populate_specs through the ragged front end: the clips as they were decoded -- any length, mono or stereo,
+        any rate -- in one call; the spectrograms come back in one device->host copy and the per-clip NaN / Inf flags
+        in another."""
+        st = self.spec_transformer
+        raw, names = [], []
+        for i, audio_file_path in found:
+            if not audio_file_path:
+                continue
+            if audio_file_path in decoded:
+                got, status = decoded[audio_file_path]
+                if got is None and status == _FLAC_UNSUPPORTED and _torchaudio is not None:
+                    got = _torchaudio.load(audio_file_path)
+                if got is None:
+                    self.logger.info(f"skipping {audio_file_path}: Failed to decode audio.")
+                    continue
+            else:
+                got = self.load_waveform(audio_file_path)
+                if got is None:
+                    continue
+            raw.append(got)
+            names.append((i, audio_file_path))
+        if not raw:
+            return []
+        out, T, first, bad = st.backend.frontend_ragged([w for w, _ in raw], [sr for _, sr in raw], self.config.common_sr,
+                                                        st.n_fft, st.hop_length, st.n_mels, fb=st.fb)
+        out, bad = out.cpu(), bad.cpu()
+        specs, m = [], st.n_mels
+        if (T == 0).any():
+            self.logger.debug(f"clips shorter than the reflect padding skipped: {int((T == 0).sum())}")
+        for j, (i, path) in enumerate(names):
+            if T[j] == 0:
+                continue
+            spec = out[m * int(first[j]): m * (int(first[j]) + int(T[j]))].view(m, int(T[j]))
+            if int(bad[j]):
+                self.check_for_nan_inf(spec, f"spectrogram {i}")
+                self.logger.debug(f"Bad file: {path}")
+                continue
+            specs.append({"filename": os.path.basename(path), "spec": spec})
+        return specs
+
     def find_audio_file(self, ytid):
         audio_file_path = None
         for source_set in self.config.audio_source_sets:
@@ -183,14 +232,21 @@ class SpectrogramGenerator:
         self.logger.debug(f"Audio file not found: {audio_file_path}")
         return None
 
-    def preprocess_waveform(self, audio_file_path):
+    def load_waveform(self, audio_file_path):
+        """-> (waveform [C, L], sample_rate), or None for a file that fails to decode (logged and skipped)."""
         try:
-            waveform, sr = _load_audio(Path(audio_file_path))
+            return _load_audio(Path(audio_file_path))
         except RuntimeError as e:
             if str(e) == "Failed to decode audio.":
                 self.logger.info(f"skipping {audio_file_path}: {e}")
                 return None
             raise
+
+    def preprocess_waveform(self, audio_file_path):
+        got = self.load_waveform(audio_file_path)
+        if got is None:
+            return None
+        waveform, sr = got
         waveform = self.convert_to_mono(waveform)
         waveform = self.resample(waveform, sr)
         return waveform

@@ -144,6 +144,79 @@ int at_logmel_minmax_f32(at_ctx* ctx, const float* wave, int64_t n_clips, int64_
                          int sample_rate, int n_fft, int hop, int n_mels, const float* fb_or_null,
                          float* out, int layout, void* stream);
 
+/* ---- ragged front end: mono mix, resampler and log-mel for clips of any length, channel count and rate -----------
+ * What SpectrogramGenerator.populate_specs does per clip (convert_to_mono, resample, generate_mel_spectrogram:
+ * processors/spectrogram_generator.py:105-126), for a whole batch of unequal clips with one launch per rate pair
+ * present and one log-mel launch.  Same bits as at_resample_f32 then at_logmel_f32 on each clip alone.
+ *
+ * at_frontend_plan_host (no GPU work) lays the batch out.  Input: one at_frontend_clip_in per clip -- its [C][L]
+ * block starts `offset` floats into the input buffer, rows `row_stride` floats apart; C is 1 or 2 (more channels are
+ * mixed by the caller and enter as mono).  Output:
+ *   plan[n_clips]    one record per clip: resampled length, where its mono row lies in the intermediate buffer (a
+ *                    multiple of 4 floats, so 16-byte loads apply), its frames T = at_num_frames(out_length, hop) and
+ *                    first output frame (exclusive prefix sum), its group, and the prefixes the kernels search to go
+ *                    from a block or frame number to the clip.  A clip with out_length <= n_fft/2 is too short for
+ *                    the reflect padding: too_short = 1, no frames.
+ *   order[n_clips]   clip indices sorted by group (stable); group g owns order[first .. first + count).
+ *   groups           one record per reduced rate pair (orig/g, new/g), in order of first appearance: 44100 -> 22050
+ *                    and 48000 -> 24000 are one group.  Clips already at common_sr form a group with no filter.
+ *                    *totals.n_groups receives the number of groups; more than groups_capacity is an error.
+ *   totals           int64 sums: floats of the intermediate buffer, frames, blocks, too-short clips.
+ * The plan is uploaded as it is (plan and order) and handed to the two device calls, which trust it. */
+typedef struct at_frontend_clip_in {
+    int64_t offset, row_stride, length;
+    int32_t channels, rate;
+} at_frontend_clip_in;
+
+typedef struct at_frontend_clip {
+    int64_t in_offset, in_row_stride, in_length;
+    int64_t out_length;       /* at_resample_length(in_length, rate, common_sr) */
+    int64_t mono_offset;      /* floats into the intermediate buffer, a multiple of 4 */
+    int64_t first_frame;      /* exclusive prefix sum of n_frames */
+    int64_t first_block16;    /* exclusive prefix sums of ceil(n_frames / 16) and ceil(n_frames / 32): the tuned */
+    int64_t first_block32;    /*   n_fft = 512 kernel works on blocks of 16 or 32 frames of one clip */
+    int64_t rs_first_block;   /* exclusive prefix sum, within the group, of the clip's resampler blocks */
+    int32_t n_frames;         /* 0 when too short */
+    int32_t channels, group, too_short;
+} at_frontend_clip;
+
+#define AT_FRONTEND_COPY 0    /* no filter: copy or mix */
+#define AT_FRONTEND_SIMPLE 1  /* one thread per output sample */
+#define AT_FRONTEND_TILED 2   /* input span staged in LDS (what at_resample_f32 uses whenever it fits) */
+
+typedef struct at_frontend_group {
+    int64_t first, count;     /* slice of order[] */
+    int64_t n_blocks;         /* workgroups of the group's launch */
+    int64_t out_per_block;    /* output samples per workgroup */
+    int32_t orig_freq, new_freq;   /* the rate pair of the group's first clip, as given */
+    int32_t orig, nw;         /* reduced by their gcd */
+    int32_t width, K;         /* filter half width and taps per phase; 0 with no filter */
+    int32_t mode, TI;         /* AT_FRONTEND_*; TILED: input steps per workgroup */
+} at_frontend_group;
+
+typedef struct at_frontend_totals {
+    int64_t mono_floats, n_frames, n_blocks16, n_blocks32, n_short, n_groups;
+} at_frontend_totals;
+
+int at_frontend_plan_host(const at_frontend_clip_in* clips, int64_t n_clips, int common_sr, int n_fft, int hop,
+                          at_frontend_clip* plan, int32_t* order, at_frontend_group* groups, int64_t groups_capacity,
+                          at_frontend_totals* totals);
+
+/* One group of a plan: every clip of it is read from in + in_offset ([C][L], C = 1 passes through, C = 2 is
+ * (l + r) * 0.5f, torch.mean's bits), resampled with at_resample_f32's arithmetic (tap order included) and written to
+ * mono + mono_offset.  plan_dev, order_dev: DEVICE copies of the plan's arrays; group: the HOST record.  One launch. */
+int at_mix_resample_ragged_f32(at_ctx* ctx, const float* in, const at_frontend_clip* plan_dev, const int32_t* order_dev,
+                               const at_frontend_group* group, float* mono, void* stream);
+
+/* at_logmel_f32 for all clips of a plan in one launch: clip i is mono + mono_offset, out_length samples, reflected at
+ * its own edges.  Every n_fft, hop, n_mels and filterbank at_logmel_f32 accepts.  out: mel-major, clip i is a
+ * contiguous [n_mels][n_frames] block at n_mels * first_frame floats; frame-major, [totals.n_frames][n_mels] (with or
+ * without fuse_l2norm).  bad: int32 [n_clips], non-zero where a value stored for the clip is NaN or +-Inf.
+ * totals: the HOST record of the plan.  No limit of 65535 clips. */
+int at_logmel_ragged_f32(at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev, int64_t n_clips,
+                         const at_frontend_totals* totals, int sample_rate, int n_fft, int hop, int n_mels,
+                         const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad, void* stream);
+
 /* Nearest centroid under squared L2 (IndexFlatL2.search(x, 1)):
  *   dis(i,j) = max(0, (|x_i|^2 + |c_j|^2) - 2 <x_i, c_j>), all fp32, inner products and norms as
  *   ascending-index fmaf chains (v_mfma_f32_32x32x2_f32); ids[i] = lowest j attaining the minimum.
