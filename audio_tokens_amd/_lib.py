@@ -118,6 +118,7 @@ SIGNATURES = {
     "at_frontend_plan_host": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "at_mix_resample_ragged_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "at_logmel_ragged_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "at_logmel_ragged_minmax_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

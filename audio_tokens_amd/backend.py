@@ -356,7 +356,7 @@ class HipBackend(HostHelpers):
         return out[0] if squeeze else out
 
     def frontend_ragged(self, clips, rates, common_sr, n_fft, hop, n_mels, fb=None, frame_major=False, l2norm=False,
-                        pad_value=None):
+                        pad_value=None, minmax=False):
         """Mono mix, resampler and log-mel for a batch of clips of any length, channel count and sample rate: one
         native call per rate pair present and one log-mel call, whatever the lengths (at_mix_resample_ragged_f32,
         at_logmel_ragged_f32).  Same bits as torch.mean, resample() and logmel() on each clip alone.
@@ -368,7 +368,10 @@ class HipBackend(HostHelpers):
         (frame_major: [sum T_i, n_mels], rows first_frame[i] .. + T_i); n_frames (int32) and first_frame (int64) are
         numpy arrays, T_i = 0 for a clip too short for the reflect padding (resampled length <= n_fft / 2); bad is a
         device int32 [n_clips], non-zero where the clip's output holds a NaN or Inf.  pad_value (tests): what the
-        intermediate buffer's padding between clips is filled with."""
+        intermediate buffer's padding between clips is filled with.
+        minmax: every clip's spectrogram becomes (spec - min) / (max - min), SpectrogramGenerator.normalize_spectrogram's
+        bits, before the unit rows if any (at_logmel_ragged_minmax_f32: still one log-mel call); bad is then set from
+        the scaled values, so a constant clip (0 / 0) is flagged too."""
         if isinstance(clips, tuple):
             flat, table = clips
             clips = [flat[o:o + C * L].view(C, L) for o, C, L in table]
@@ -433,7 +436,8 @@ class HipBackend(HostHelpers):
                     self.ctx.handle, _vp(base), plan_ptr, order_ptr, _vp(groups.ctypes.data + g * groups.itemsize),
                     _ptr(mono), self._stream()))
                 self.frontend_calls += 1
-            _lib.check(self.lib.at_logmel_ragged_f32(
+            logmel_ragged = self.lib.at_logmel_ragged_minmax_f32 if minmax else self.lib.at_logmel_ragged_f32
+            _lib.check(logmel_ragged(
                 self.ctx.handle, _ptr(mono), plan_ptr, n, _np_ptr(totals), common_sr, n_fft, hop, n_mels, _ptr(fbt),
                 _ptr(out), _lib.AT_LAYOUT_FRAME_MAJOR if frame_major else _lib.AT_LAYOUT_MEL_MAJOR, 1 if l2norm else 0,
                 _ptr(bad), self._stream()))

@@ -143,6 +143,119 @@ __global__ void __launch_bounds__(256) minmax_apply_kernel(float* __restrict__ x
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < clip_elems; e += (long)gridDim.x * 256) p[e] = __fdiv_rn(p[e] - lo, range);
 }
 
+// ---- the ragged forms (at_logmel_ragged_minmax_f32) ---------------------------------------------------------------------
+// The output of a plan is one flat run of floats in either layout: clip i owns [first_frame, first_frame + n_frames) x
+// n_mels of it.  A wavefront takes MM_CHUNK consecutive floats at a time and walks the pieces of clips inside them: the
+// clip of a piece is the one whose first_frame is the last one <= the piece's first frame (binary search, as the
+// per-frame kernels do; a clip without frames shares its prefix with the clip behind it and is never found), the
+// piece ends where the clip or the chunk does.  Everything that decides the walk is the same in all 64 lanes.
+constexpr int MM_CHUNK = 4096;
+struct RaggedMinmaxParams {
+    float* x;                       // [n_frames][n_mels] floats, clip after clip
+    long total;                     // n_frames * n_mels
+    int n_mels, vec;                // vec: n_mels % 4 == 0 and x 16-byte aligned, so every piece is whole aligned quads
+    const at_frontend_clip* plan;
+    long n_clips;
+    unsigned* mm;                   // [n_clips][4] records, as minmax_init_kernel leaves them
+    int* clip_bad;                  // [n_clips] (the scaling pass)
+};
+template <typename Body>
+__device__ __forceinline__ void ragged_pieces(const RaggedMinmaxParams& p, Body body) {
+    const int lane = threadIdx.x & 63;
+    const long wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+    const long n_waves = (long)gridDim.x * (blockDim.x >> 6);
+    for (long a = wave * MM_CHUNK; a < p.total; a += n_waves * MM_CHUNK) {
+        const long b = min(p.total, a + MM_CHUNK);
+        for (long s = a; s < b;) {
+            const long g = s / p.n_mels;
+            long lo = 0, hi = p.n_clips;
+            while (hi - lo > 1) {
+                const long mid = (lo + hi) >> 1;
+                if (p.plan[mid].first_frame <= g) lo = mid;
+                else hi = mid;
+            }
+            const long end = min(b, (p.plan[lo].first_frame + p.plan[lo].n_frames) * p.n_mels);
+            if (end <= s) return;   // (a plan that does not cover the output: never loop on it)
+            body(lo, s, end, lane);
+            s = end;
+        }
+    }
+}
+
+// The reduction pass behind the transforms that do not collect the extremes themselves (every n_fft but 512): the same
+// records, ordered keys and NaN flag as the tuned kernel leaves, one pair of atomics per piece.  4 B read per value.
+__global__ void __launch_bounds__(256) minmax_scale_kernel_ragged_extremes(RaggedMinmaxParams p) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    ragged_pieces(p, [&](long clip, long s, long end, int lane) {
+        float lo = __builtin_inff(), hi = -__builtin_inff();
+        int nan = 0;
+        if (p.vec) {
+            const f4* x4 = reinterpret_cast<const f4*>(p.x);
+            for (long q = (s >> 2) + lane; q < (end >> 2); q += 64) {
+                const f4 v = x4[q];
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    nan |= v[e] != v[e];
+                    lo = __builtin_fminf(lo, v[e]);
+                    hi = __builtin_fmaxf(hi, v[e]);
+                }
+            }
+        } else {
+            for (long e = s + lane; e < end; e += 64) {
+                const float v = p.x[e];
+                nan |= v != v;
+                lo = __builtin_fminf(lo, v);
+                hi = __builtin_fmaxf(hi, v);
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            lo = __builtin_fminf(lo, __shfl_xor(lo, off));
+            hi = __builtin_fmaxf(hi, __shfl_xor(hi, off));
+            nan |= __shfl_xor(nan, off);
+        }
+        if (lane == 0) {
+            if (lo <= hi) {
+                atomicMin(&p.mm[4 * clip], ordered_key(lo));
+                atomicMax(&p.mm[4 * clip + 1], ordered_key(hi));
+            }
+            if (nan) atomicOr(&p.mm[4 * clip + 2], 1u);
+        }
+    });
+}
+
+// minmax_apply_kernel for the clips of a plan, either layout: the same two subtractions and one IEEE division per value.
+// A clip is flagged where a value stored for it is not finite -- the reference checks for NaN / Inf after normalising
+// (processors/spectrogram_generator.py:107-110), so a constant clip (0 / 0) is skipped like one with a NaN sample.
+// 8 B per value.
+__global__ void __launch_bounds__(256) minmax_apply_kernel_ragged(RaggedMinmaxParams p) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    ragged_pieces(p, [&](long clip, long s, long end, int lane) {
+        float lo = key_to_float(p.mm[4 * clip]), hi = key_to_float(p.mm[4 * clip + 1]);
+        if (p.mm[4 * clip + 2]) lo = hi = __builtin_nanf("");
+        const float range = hi - lo;
+        int flagged = 0;
+        if (p.vec) {
+            f4* x4 = reinterpret_cast<f4*>(p.x);
+            for (long q = (s >> 2) + lane; q < (end >> 2); q += 64) {
+                f4 v = x4[q];
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    v[e] = __fdiv_rn(v[e] - lo, range);
+                    flagged |= not_finite(v[e]);
+                }
+                x4[q] = v;
+            }
+        } else {
+            for (long e = s + lane; e < end; e += 64) {
+                const float v = __fdiv_rn(p.x[e] - lo, range);
+                flagged |= not_finite(v);
+                p.x[e] = v;
+            }
+        }
+        if (flagged) p.clip_bad[clip] = 1;   // (every writer stores the same value)
+    });
+}
+
 // PF: the next block's samples are prefetched through registers (needs a block of at most PREFETCH_REGS x WG x 4
 // samples); otherwise they are staged at the top of the block.
 // RG: the ragged form.
@@ -537,35 +650,54 @@ static int logmel_impl(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t 
 
 // at_logmel_f32 for the clips of an at_frontend_plan_host plan, one launch (include/audio_tokens_amd.h).  The same
 // kernels over the same tables as the uniform call; only where a block or frame finds its clip differs.
-extern "C" int at_logmel_ragged_f32(at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev, int64_t n_clips,
-                                    const at_frontend_totals* totals, int sample_rate, int n_fft, int hop, int n_mels,
-                                    const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad,
-                                    void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_logmel_args("at_logmel_ragged_f32", ctx, n_fft, hop, n_mels, layout, fuse_l2norm);
+// minmax (at_logmel_ragged_minmax_f32): every clip becomes (spec - min) / (max - min) before the unit rows, if any.
+// n_fft = 512: the tuned kernel collects every clip's extremes while a block is still in LDS, keyed by the block's
+// clip; every other size: the transform as it is, then a reduction pass over its output.  Then the scaling pass, which
+// sets the clips' flags, and -- fuse_l2norm -- the stand-alone unit rows over the scaled rows, in place (the kernel's
+// own unit rows stay off: the rows are scaled first).
+static int logmel_ragged_impl(const char* who, at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev,
+                              int64_t n_clips, const at_frontend_totals* totals, int sample_rate, int n_fft, int hop,
+                              int n_mels, const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad,
+                              bool minmax, hipStream_t stream) {
+    int rc = check_logmel_args(who, ctx, n_fft, hop, n_mels, layout, fuse_l2norm);
     if (rc) return rc;
-    AT_REQUIRE(n_clips >= 0 && n_clips < (1LL << 31), "at_logmel_ragged_f32: n_clips out of range");
+    AT_REQUIRE(n_clips >= 0 && n_clips < (1LL << 31), "%s: n_clips out of range", who);
     if (n_clips == 0) return AT_OK;
-    AT_REQUIRE(totals && plan_dev && bad, "at_logmel_ragged_f32: null pointer");
+    AT_REQUIRE(totals && plan_dev && bad, "%s: null pointer", who);
     AT_REQUIRE(totals->n_frames >= 0 && totals->n_blocks16 >= 0 && totals->n_blocks32 >= 0 &&
                    totals->n_blocks32 <= totals->n_blocks16 && totals->n_blocks16 <= totals->n_frames,
-               "at_logmel_ragged_f32: bad totals");
+               "%s: bad totals", who);
     AT_HIP(hipSetDevice(ctx->device));
     AT_HIP(hipMemsetAsync(bad, 0, (size_t)n_clips * sizeof(int32_t), stream));
     if (totals->n_frames == 0) return AT_OK;   // every clip too short
-    AT_REQUIRE(mono && out, "at_logmel_ragged_f32: null pointer");
+    AT_REQUIRE(mono && out, "%s: null pointer", who);
+    RaggedMinmaxParams mp{};
+    long mgrid = 0;
+    if (minmax) {
+        mp.mm = static_cast<unsigned*>(at_ws(ctx, WS_LOGMEL_MINMAX, (size_t)n_clips * 16, stream));
+        if (!mp.mm) return AT_E_NOMEM;
+        AT_LAUNCH(minmax_init_kernel, dim3((unsigned)((n_clips + 255) / 256)), dim3(256), 0, stream, mp.mm, (long)n_clips);
+        mp.x = out; mp.total = (long)totals->n_frames * n_mels; mp.n_mels = n_mels;
+        mp.vec = (n_mels & 3) == 0 && at_aligned16(out);
+        mp.plan = plan_dev; mp.n_clips = n_clips; mp.clip_bad = bad;
+        // one wavefront per MM_CHUNK floats, at most eight workgroups per CU walking the rest
+        mgrid = ((mp.total + MM_CHUNK - 1) / MM_CHUNK + 3) / 4;
+        if (mgrid > 8L * ctx->n_cus) mgrid = 8L * ctx->n_cus;
+    }
+    bool rows_done = false;   // the unit rows came out of the log-mel kernel
     if (n_fft != NFFT) {
         rc = at_logmel_any(ctx, mono, n_clips, 0, 0, sample_rate, n_fft, hop, n_mels, fb_or_null, out,
                            layout == AT_LAYOUT_FRAME_MAJOR, plan_dev, bad, totals->n_frames, stream);
         if (rc) return rc;
+        if (minmax) AT_LAUNCH(minmax_scale_kernel_ragged_extremes, dim3((unsigned)mgrid), dim3(256), 0, stream, mp);
     } else {
         RaggedLogmelParams p;
         Setup512 su;
-        rc = setup_512(ctx, sample_rate, hop, n_mels, fb_or_null, fuse_l2norm, stream, p, su);
+        rc = setup_512(ctx, sample_rate, hop, n_mels, fb_or_null, minmax ? 0 : fuse_l2norm, stream, p, su);
         if (rc) return rc;
         p.wave = mono; p.n_clips = n_clips; p.L = 0; p.wave_stride = 0; p.T = 0; p.blocks_per_clip = 0;
         p.out = out; p.frame_major = layout == AT_LAYOUT_FRAME_MAJOR;
-        p.minmax = nullptr;
+        p.minmax = mp.mm;
         p.plan = plan_dev; p.clip_bad = bad;
         p.n_blocks = (long)(p.fpb == 32 ? totals->n_blocks32 : totals->n_blocks16);
         AT_RAISE_LDS(ctx, (logmel_kernel<true, true>), su.lds);
@@ -574,16 +706,33 @@ extern "C" int at_logmel_ragged_f32(at_ctx* ctx, const float* mono, const at_fro
         if (grid > p.n_blocks) grid = p.n_blocks;
         if (su.pf) AT_LAUNCH((logmel_kernel<true, true>), dim3((unsigned)grid), dim3(WG), su.lds, stream, p);
         else AT_LAUNCH((logmel_kernel<false, true>), dim3((unsigned)grid), dim3(WG), su.lds, stream, p);
-        if (!fuse_l2norm || su.fuse_here) return AT_OK;
+        rows_done = su.fuse_here;
     }
-    // unit rows by the stand-alone kernel, in place.  The clips' flags, set from the dB values, hold for the unit rows:
-    // a NaN or Inf in a row makes the row NaN, and a finite row stays finite.
-    if (fuse_l2norm) {
+    if (minmax) AT_LAUNCH(minmax_apply_kernel_ragged, dim3((unsigned)mgrid), dim3(256), 0, stream, mp);
+    // unit rows by the stand-alone kernel, in place.  The clips' flags, set from the dB values (or the scaled ones), hold
+    // for the unit rows: a NaN or Inf in a row makes the row NaN, and a finite row stays finite.
+    if (fuse_l2norm && !rows_done) {
         int* flag = at_row_flag(ctx, stream);
         if (!flag) return AT_E_NOMEM;
         rc = at_l2norm_rows_flagged(ctx, out, totals->n_frames, n_mels, out, flag, stream);
     }
     return rc;
+}
+
+extern "C" int at_logmel_ragged_f32(at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev, int64_t n_clips,
+                                    const at_frontend_totals* totals, int sample_rate, int n_fft, int hop, int n_mels,
+                                    const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad,
+                                    void* stream_) {
+    return logmel_ragged_impl("at_logmel_ragged_f32", ctx, mono, plan_dev, n_clips, totals, sample_rate, n_fft, hop, n_mels,
+                              fb_or_null, out, layout, fuse_l2norm, bad, false, (hipStream_t)stream_);
+}
+
+extern "C" int at_logmel_ragged_minmax_f32(at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev, int64_t n_clips,
+                                           const at_frontend_totals* totals, int sample_rate, int n_fft, int hop, int n_mels,
+                                           const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad,
+                                           void* stream_) {
+    return logmel_ragged_impl("at_logmel_ragged_minmax_f32", ctx, mono, plan_dev, n_clips, totals, sample_rate, n_fft, hop,
+                              n_mels, fb_or_null, out, layout, fuse_l2norm, bad, true, (hipStream_t)stream_);
 }
 
 extern "C" int at_logmel_f32(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L,

@@ -12,6 +12,8 @@
         (processors/cluster_creator.py:115-117)
     torchaudio.load (of a .flac file)                     ->  load_flac, load_flac_batch
         (processors/spectrogram_generator.py:99)
+    get_spectrogram + get_sequence                        ->  AudioTokenizer
+        (tools/manual_tester.py: audio -> tokens against a trained vocabulary)
 
 Same constructor arguments, method names, return types and error behaviour as the originals for the
 subset the reference uses.  All arithmetic happens in libaudio_tokens_amd.so (HIP, gfx950); this
@@ -34,7 +36,7 @@ import torch
 from .backend import default_backend
 
 __all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "normalize_rows", "silhouette_samples",
-           "silhouette_score", "load_flac", "load_flac_batch"]
+           "silhouette_score", "load_flac", "load_flac_batch", "AudioTokenizer"]
 
 
 def _is_host(x) -> bool:
@@ -111,18 +113,19 @@ class LogMelSpectrogram:
                         self.n_mels, fb=self.fb)
         return out.reshape(*lead, self.n_mels, out.shape[-1])
 
-    def batch(self, waveforms, sample_rates=None):
+    def batch(self, waveforms, sample_rates=None, normalize=False):
         """Clips of any length, channel count and sample rate -> a list of [n_mels, T_i] dB spectrograms in input order,
         views of one flat device tensor; None where a clip is too short for the reflect padding (its length at
         self.sample_rate <= n_fft / 2).  waveforms: [C_i, L_i] or [L_i] tensors; sample_rates: one per clip (default:
         all at self.sample_rate).  Stereo is mixed to mono and other rates are resampled to self.sample_rate, with the
         bits of torch.mean and Resample per clip, in one launch per rate pair present and one log-mel launch
-        (HipBackend.frontend_ragged).  self.last_bad: device int32 per clip, non-zero where its spectrogram holds a NaN
-        or Inf."""
+        (HipBackend.frontend_ragged).  normalize: every spectrogram scaled to (spec - min) / (max - min), the
+        reference's normalize_spectrogram, in the same log-mel call.  self.last_bad: device int32 per clip, non-zero
+        where its spectrogram (the scaled one under normalize: a constant clip gives 0 / 0) holds a NaN or Inf."""
         be = self.backend
         rates = self.sample_rate if sample_rates is None else sample_rates
         out, T, first, self.last_bad = be.frontend_ragged(waveforms, rates, self.sample_rate, self.n_fft, self.hop_length,
-                                                          self.n_mels, fb=self.fb)
+                                                          self.n_mels, fb=self.fb, minmax=normalize)
         m = self.n_mels
         return [None if T[i] == 0 else out[m * int(first[i]): m * (int(first[i]) + int(T[i]))].view(m, int(T[i]))
                 for i in range(len(T))]
@@ -701,6 +704,76 @@ class IndexFlatL2:
         else:
             I, D = be.knn(x, self._c, k)
         return (be.to_host(D), be.to_host(I)) if host else (D, I)
+
+
+class AudioTokenizer:
+    """Audio -> token ids against a trained vocabulary, without a spectrogram leaving the device: what the reference
+    does with get_spectrogram + get_sequence (tools/manual_tester.py), and what SpectrogramGenerator.run() followed by
+    SpecTokenizer.run() compute through .npy files -- same tokens.
+
+    centroids: the vocabulary, [k, d] (numpy or tensor), or an IndexFlatL2 that holds it.  d = n_mels, or
+    n_mels * num_kernels with `conv`, the nn.Conv1d(1, num_kernels, kernel_size, padding) of config.use_convolution.
+    normalize: config.normalize, the per-clip (spec - min) / (max - min).  One batch is one ragged front-end call
+    (frame-major rows; unit rows and the scaling in the same log-mel call), the convolution and its row normalisation if
+    any, one nearest-centroid search, and two device->host copies: the tokens and the per-clip flags."""
+
+    def __init__(self, centroids, sample_rate=22050, n_fft=512, hop_length=128, n_mels=64, normalize=False, conv=None,
+                 fb=None, backend=None):
+        self.backend = be = backend or default_backend()
+        if isinstance(centroids, IndexFlatL2):
+            self.index = centroids
+        else:
+            c = be._f32(centroids)
+            self.index = IndexFlatL2(c.shape[1], backend=be)
+            self.index.add(c)
+        self.sample_rate, self.n_fft, self.hop_length, self.n_mels = sample_rate, n_fft, hop_length, n_mels
+        self.normalize, self.conv = bool(normalize), conv
+        self.fb = None if fb is None else be._f32(fb)
+        d = n_mels * (conv.weight.shape[0] if conv is not None else 1)
+        assert self.index.d == d, f"centroids are [k, {self.index.d}], the frames [n, {d}]"
+        self.last_tokens = None   # device int64: the tokens of the last batch's kept clips, clip after clip
+
+    def encode(self, waveforms, sample_rates=None):
+        """-> one entry per clip, in input order: its tokens, a host int64 tensor [T_i], or None where the reference
+        would skip the clip (too short for the reflect padding; a NaN or Inf in its spectrogram -- under normalize, a
+        constant clip too).  waveforms: what HipBackend.frontend_ragged takes -- [C_i, L_i] or [L_i] tensors on either
+        side, or (flat, table) as the FLAC decoder leaves it; sample_rates: one per clip, or one for all (default:
+        self.sample_rate)."""
+        be = self.backend
+        n = len(waveforms[1]) if isinstance(waveforms, tuple) else len(waveforms)
+        self.last_tokens = None
+        if n == 0:
+            return []
+        rates = self.sample_rate if sample_rates is None else sample_rates
+        rows, T, first, bad = be.frontend_ragged(waveforms, rates, self.sample_rate, self.n_fft, self.hop_length, self.n_mels,
+                                                 fb=self.fb, frame_major=True, l2norm=self.conv is None,
+                                                 minmax=self.normalize)
+        if rows.shape[0] == 0:
+            return [None] * n
+        if self.conv is not None:
+            with torch.no_grad():
+                bias = self.conv.bias.detach() if self.conv.bias is not None else None
+                rows = be.l2norm_rows(be.conv1d_mel(rows, self.conv.weight.detach(), bias, padding=int(self.conv.padding[0])))
+        tokens_dev, _ = self.index.assign(rows, want_dist=False)
+        tokens, bad = torch.from_numpy(be.to_host(tokens_dev)), be.to_host(bad)
+        keep = (T > 0) & (bad == 0)
+        # (the rows of a flagged clip hold NaN and their tokens mean nothing: dropped here, and from last_tokens)
+        self.last_tokens = tokens_dev if not bad.any() else tokens_dev[be.from_host(np.repeat(keep, T))]
+        return [tokens[int(first[i]): int(first[i]) + int(T[i])] if keep[i] else None for i in range(n)]
+
+    def encode_files(self, paths):
+        """encode() for audio files: the batch's .flac files in one device decode, other formats on the host, as
+        SpectrogramGenerator reads them.  None for a file that does not decode, too."""
+        import logging
+
+        from .processors.spectrogram_generator import decode_batch
+        got = decode_batch(paths, self.backend, logging.getLogger(__name__))
+        live = [i for i, g in enumerate(got) if g is not None]
+        tokens = self.encode([got[i][0] for i in live], [got[i][1] for i in live])
+        out = [None] * len(got)
+        for i, t in zip(live, tokens):
+            out[i] = t
+        return out
 
 
 def _check_random_state(seed):

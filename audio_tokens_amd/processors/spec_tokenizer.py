@@ -6,7 +6,8 @@ Same constructor, methods and artefacts (tokenized_audio/{train,validation}/<ste
 concatenate, normalise rows, search(.,1), slice per file, save) is the reference's.  A batch
 crosses to the device once (convolution, row normalisation and the search run there); the token
 statistics at the end of the train split are computed on the device from a histogram accumulated while
-tokenising, and the plots are drawn only if matplotlib is importable.
+tokenising, and the plots are drawn only if matplotlib is importable.  tokenize_audio() goes from audio files to the same
+tokens without the spectrogram files in between.
 """
 import logging
 import shutil
@@ -109,6 +110,38 @@ class SpecTokenizer:
             return tokens.tolist() if self.return_token_lists else []
 
         return []
+
+    def tokenize_audio(self, audio_files, tokenized_dir=None):
+        """Audio files -> {file stem: tokens (numpy int64 [T])}, straight from the audio: no spectrogram file is written
+        or read, and no spectrogram leaves the device (ops.AudioTokenizer, built from the config's front-end fields,
+        `normalize`, and this object's convolution under use_convolution).  Same tokens as SpectrogramGenerator.run()
+        followed by run() on the same clips; clips the generator would skip (undecodable, too short, NaN / Inf) have
+        no entry.  Batches of tokenizer_batch_size files.  With tokenized_dir, <stem>.npy is written there as
+        process_batch writes it.  The tokens join the device histogram behind analyze_tokens()."""
+        from ..ops import AudioTokenizer
+        cfg = self.config
+        be = self.index.backend
+        tok = AudioTokenizer(self.index, sample_rate=cfg.common_sr, n_fft=cfg.n_fft, hop_length=cfg.hop_length,
+                             n_mels=cfg.n_mels, normalize=cfg.normalize, conv=self.conv if cfg.use_convolution else None,
+                             backend=be)
+        if tokenized_dir is not None:
+            tokenized_dir = Path(tokenized_dir)
+            tokenized_dir.mkdir(parents=True, exist_ok=True)
+        audio_files = [Path(f) for f in audio_files]
+        result = {}
+        for i in range(0, len(audio_files), cfg.tokenizer_batch_size):
+            batch_files = audio_files[i: i + cfg.tokenizer_batch_size]
+            batch_tokens = tok.encode_files(batch_files)
+            if tok.last_tokens is not None and tok.last_tokens.numel() > 0:
+                hist = be.token_histogram(tok.last_tokens, max(1, self.index.ntotal))
+                self._hist = hist if self._hist is None else self._hist + hist
+            for audio_file, tokens in zip(batch_files, batch_tokens):
+                if tokens is None:
+                    continue
+                result[audio_file.stem] = tokens.numpy()
+                if tokenized_dir is not None:
+                    np.save(tokenized_dir / f"{audio_file.stem}.npy", result[audio_file.stem])
+        return result
 
     def _convolve_device(self, frames):
         """frames [n, n_mels] (device) -> [n, num_kernels * n_mels] (device): the module's Conv1d along the mel axis, feature

@@ -7,7 +7,8 @@ Same constructor, methods, outputs (spectrograms/{train,validation}/<ytid>.npy, 
     resampler launch per rate pair present and ONE fused STFT -> mel -> dB launch (the reference launches a dozen
     kernels per clip); the whole batch comes back in one device->host copy before the per-file np.save, the per-clip
     NaN / Inf flags in another (SpectrogramGenerator.ragged; DESIGN.md section 6d);
-  * with normalize=True, or ragged=False: one resampler call per clip (ops.Resample) and one launch per clip length.
+    with normalize=True the per-clip (spec - min) / (max - min) rides in the same log-mel call;
+  * with ragged=False: one resampler call per clip (ops.Resample) and one launch per clip length.
 .flac files are decoded on the device (ops.load_flac / load_flac_batch: all of a batch in one call) and stay there
 through the mono mix and the resampler.  Other audio is decoded on the CPU: torchaudio.load if torchaudio is
 importable, otherwise PCM/float .wav through the standard library and raw float32 .npy waveforms (used by the
@@ -77,10 +78,45 @@ def _load_audio(path: Path):
     raise RuntimeError("Failed to decode audio.")
 
 
+def load_waveform(audio_file_path, logger):
+    """-> (waveform [C, L], sample_rate), or None for a file that fails to decode (logged and skipped)."""
+    try:
+        return _load_audio(Path(audio_file_path))
+    except RuntimeError as e:
+        if str(e) == "Failed to decode audio.":
+            logger.info(f"skipping {audio_file_path}: {e}")
+            return None
+        raise
+
+
+def decode_batch(paths, backend, logger, load=None):
+    """The files of one batch as they decode -> one entry per path, in order: (waveform [C, L], sample_rate), or None
+    for a path that is None and for a file that fails to decode (logged and skipped, as the reference does).  The
+    batch's .flac files go through one device decode and stay on the device; every other file through `load`
+    (default: load_waveform).
+    Shared by SpectrogramGenerator and ops.AudioTokenizer.encode_files."""
+    paths = [Path(p) if p else None for p in paths]
+    flacs = [p for p in paths if p and p.suffix.lower() == ".flac"]
+    decoded = dict(zip(flacs, zip(load_flac_batch(flacs, backend=backend), backend.flac_status))) if flacs else {}
+    out = []
+    for path in paths:
+        got = None
+        if path in decoded:
+            got, status = decoded[path]
+            if got is None and status == _FLAC_UNSUPPORTED and _torchaudio is not None:
+                got = _torchaudio.load(path)   # (Ogg-FLAC, 32-bit samples: as _load_audio does)
+            if got is None:
+                logger.info(f"skipping {path}: Failed to decode audio.")
+        elif path:
+            got = load(path) if load else load_waveform(path, logger)
+        out.append(got)
+    return out
+
+
 class SpectrogramGenerator:
     # A/B switch: True = batches go through the ragged front end (one launch per rate pair present, one log-mel launch,
-    # two device->host copies, whatever the clip lengths); False = one resampler call per clip and one log-mel launch
-    # per distinct length.  Both settings write the same files.  (normalize=True batches always take the second route.)
+    # two device->host copies, whatever the clip lengths, with or without normalize); False = one resampler call per
+    # clip and one log-mel launch per distinct length.  Both settings write the same files.
     ragged = True
 
     def __init__(self, config):
@@ -125,12 +161,12 @@ class SpectrogramGenerator:
         The tensors are views of per-length batch results that already live on the host side of
         one bulk copy when `.cpu()` is called on them (they share storage per batch)."""
         found = [(i, self.find_audio_file(ytid)) for i, ytid in enumerate(source_files)]
+        if self.ragged:
+            return self._populate_specs_ragged(found)
         # the batch's .flac files in one device decode; the waveforms stay on the device
         be = self.spec_transformer.backend
         flacs = [p for _, p in found if p and p.suffix.lower() == ".flac"]
         decoded = dict(zip(flacs, zip(load_flac_batch(flacs, backend=be), be.flac_status))) if flacs else {}
-        if self.ragged and not self.config.normalize:
-            return self._populate_specs_ragged(found, decoded)
         waves, names = [], []
         for i, audio_file_path in found:
             if not audio_file_path:
@@ -180,32 +216,19 @@ class SpectrogramGenerator:
             specs.append({"filename": os.path.basename(names[j][1]), "spec": specs_by_j[j]})
         return specs
 
-    def _populate_specs_ragged(self, found, decoded):
+    def _populate_specs_ragged(self, found):
         """populate_specs through the ragged front end: the clips as they were decoded -- any length, mono or stereo,
-        any rate -- in one call; the spectrograms come back in one device->host copy and the per-clip NaN / Inf flags
-        in another."""
+        any rate -- in one call, the per-clip min-max scaling of normalize=True included; the spectrograms come back
+        in one device->host copy and the per-clip NaN / Inf flags in another."""
         st = self.spec_transformer
-        raw, names = [], []
-        for i, audio_file_path in found:
-            if not audio_file_path:
-                continue
-            if audio_file_path in decoded:
-                got, status = decoded[audio_file_path]
-                if got is None and status == _FLAC_UNSUPPORTED and _torchaudio is not None:
-                    got = _torchaudio.load(audio_file_path)
-                if got is None:
-                    self.logger.info(f"skipping {audio_file_path}: Failed to decode audio.")
-                    continue
-            else:
-                got = self.load_waveform(audio_file_path)
-                if got is None:
-                    continue
-            raw.append(got)
-            names.append((i, audio_file_path))
+        got = decode_batch([p for _, p in found], st.backend, self.logger, load=self.load_waveform)
+        raw = [g for g in got if g is not None]
+        names = [f for f, g in zip(found, got) if g is not None]
         if not raw:
             return []
         out, T, first, bad = st.backend.frontend_ragged([w for w, _ in raw], [sr for _, sr in raw], self.config.common_sr,
-                                                        st.n_fft, st.hop_length, st.n_mels, fb=st.fb)
+                                                        st.n_fft, st.hop_length, st.n_mels, fb=st.fb,
+                                                        minmax=bool(self.config.normalize))
         out, bad = out.cpu(), bad.cpu()
         specs, m = [], st.n_mels
         if (T == 0).any():
@@ -234,13 +257,7 @@ class SpectrogramGenerator:
 
     def load_waveform(self, audio_file_path):
         """-> (waveform [C, L], sample_rate), or None for a file that fails to decode (logged and skipped)."""
-        try:
-            return _load_audio(Path(audio_file_path))
-        except RuntimeError as e:
-            if str(e) == "Failed to decode audio.":
-                self.logger.info(f"skipping {audio_file_path}: {e}")
-                return None
-            raise
+        return load_waveform(audio_file_path, self.logger)
 
     def preprocess_waveform(self, audio_file_path):
         got = self.load_waveform(audio_file_path)

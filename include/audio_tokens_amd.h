@@ -217,6 +217,18 @@ int at_logmel_ragged_f32(at_ctx* ctx, const float* mono, const at_frontend_clip*
                          const at_frontend_totals* totals, int sample_rate, int n_fft, int hop, int n_mels,
                          const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad, void* stream);
 
+/* at_logmel_ragged_f32 followed by normalize_spectrogram (processors/spectrogram_generator.py:129-131, config.normalize)
+ * on every clip of the plan: clip i's block holds (spec - min_i) / (max_i - min_i), torch's bits (two fp32 subtractions
+ * and one IEEE division per value); a NaN anywhere in a clip makes the whole clip NaN.  Same arguments.  The extremes
+ * are collected by the tuned kernel itself at n_fft = 512 and by a reduction pass over the output at every other size;
+ * one scaling pass follows.  fuse_l2norm (frame-major): at_l2norm_rows_f32 over the SCALED rows, in place.
+ * bad: non-zero where a value stored for the clip is NaN or +-Inf AFTER the scaling, which is where the reference
+ * checks: a constant clip (digital silence: 0 / 0) is flagged like a clip with a NaN sample.  No limit of 65535 clips. */
+int at_logmel_ragged_minmax_f32(at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev, int64_t n_clips,
+                                const at_frontend_totals* totals, int sample_rate, int n_fft, int hop, int n_mels,
+                                const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad,
+                                void* stream);
+
 /* Nearest centroid under squared L2 (IndexFlatL2.search(x, 1)):
  *   dis(i,j) = max(0, (|x_i|^2 + |c_j|^2) - 2 <x_i, c_j>), all fp32, inner products and norms as
  *   ascending-index fmaf chains (v_mfma_f32_32x32x2_f32); ids[i] = lowest j attaining the minimum.

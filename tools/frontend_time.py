@@ -9,7 +9,15 @@ and the spread of --reps calls, each bracketed by a device synchronisation), the
 (resample, logmel, frontend_ragged's launches), and the bytes and number of device->host copies (Tensor.cpu).  With both
 routes at hand their spectrograms are compared bit for bit.  The tool runs unchanged on an older checkout: the numbers
 for the route before this front end are taken there, the ragged=False setting is only the cross-check.
-tools/frontend_time.py [--clips N] [--reps R] [--seed S] [--out FILE]: one JSON line per route."""
+--normalize times the same call with config.normalize = True (the per-clip min-max scaling): the ragged route on a
+checkout that has it there, the per-length route on an older one.
+--mode tokens times audio -> token files instead, on the same clips against --vocab random unit centroids:
+"tokenize_audio" (SpecTokenizer.tokenize_audio, where the class has it) and "files" (SpectrogramGenerator.run() then
+SpecTokenizer.run() through .npy spectrograms, the only route of an older checkout), one timed pass each after a warm-up
+pass, with the native front-end calls and the device->host bytes of the pass; the token files of the two are compared
+byte for byte.  The spectrogram files of the file route take 441 KB per 10 s clip: choose --clips to fit the disk.
+tools/frontend_time.py [--clips N] [--reps R] [--seed S] [--normalize] [--mode specs|tokens] [--vocab K] [--out FILE]:
+one JSON line per route."""
 import argparse
 import json
 import os
@@ -31,6 +39,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--seed", type=int, default=11)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--normalize", action="store_true")
+    ap.add_argument("--mode", choices=("specs", "tokens"), default="specs")
+    ap.add_argument("--vocab", type=int, default=1024)
     args = ap.parse_args()
     from audio_tokens_amd.audio_tokens_config import AudioTokensConfig
     from audio_tokens_amd.processors import spectrogram_generator as sg
@@ -52,7 +63,8 @@ def main():
     tmp = tempfile.mkdtemp()
     Path(tmp, "split.json").write_text(json.dumps({"train": names, "validation": []}))
     cfg = AudioTokensConfig(split_file=str(Path(tmp, "split.json")), audio_source_path=tmp, dest_spec_path=Path(tmp, "spec"),
-                            source_spec_path=Path(tmp, "spec"), spectrogram_batch_size=n)
+                            source_spec_path=Path(tmp, "spec"), spectrogram_batch_size=n, normalize=args.normalize,
+                            centroids_path=Path(tmp, "centroids.npy"), dest_tokenized_path=str(Path(tmp, "tok")))
     gen = sg.SpectrogramGenerator(cfg)
     gen.find_audio_file = lambda ytid: Path(tmp, ytid + ".dev")
     sg._load_audio = lambda path: clips[Path(path).stem]
@@ -80,6 +92,13 @@ def main():
                                 cwd=os.path.dirname(os.path.abspath(__file__))).stdout.strip()
     except OSError:
         commit = ""
+    if args.mode == "tokens":
+        lines = time_tokens(args, cfg, gen, be, count, names, commit, tmp)
+        if args.out:
+            with open(args.out, "a") as f:
+                for rec in lines:
+                    f.write(json.dumps(rec) + "\n")
+        return
     routes = [("ragged", True), ("ragged_off", False)] if hasattr(sg.SpectrogramGenerator, "ragged") else [("per_clip", None)]
     lines, results = [], {}
     for route, flag in routes:
@@ -96,7 +115,7 @@ def main():
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
         timed = times[1:]
-        rec = {"route": route, "commit": commit, "clips": n, "specs": len(specs), "distinct_lengths": len({c[0].shape[1] for c in clips.values()}),
+        rec = {"route": route, "commit": commit, "normalize": args.normalize, "clips": n, "specs": len(specs), "distinct_lengths": len({c[0].shape[1] for c in clips.values()}),
                "warmup_s": round(times[0], 4), "median_s": round(statistics.median(timed), 4), "min_s": round(min(timed), 4),
                "max_s": round(max(timed), 4), "runs_s": [round(t, 4) for t in timed],
                "native_calls": count["native"] + getattr(be, "frontend_calls", 0) - calls0,
@@ -115,6 +134,50 @@ def main():
         with open(args.out, "a") as f:
             for rec in lines:
                 f.write(json.dumps(rec) + "\n")
+
+
+def time_tokens(args, cfg, gen, be, count, names, commit, tmp):
+    """--mode tokens: audio -> token files, straight and through spectrogram files."""
+    from audio_tokens_amd.processors import SpecTokenizer
+    c = np.random.default_rng(args.seed).standard_normal((args.vocab, cfg.n_mels)).astype(np.float32)
+    np.save(cfg.centroids_path, c / np.linalg.norm(c, axis=1, keepdims=True))
+    tok = SpecTokenizer(cfg)
+    paths = [gen.find_audio_file(y) for y in names]
+    direct = Path(tmp, "direct")
+
+    def files_route():
+        gen.run()
+        tok.run()
+
+    def direct_route():
+        tok.tokenize_audio(paths, direct)
+    routes = [("files", files_route)] + ([("tokenize_audio", direct_route)] if hasattr(SpecTokenizer, "tokenize_audio") else [])
+    lines = []
+    for route, run in routes:
+        times = []
+        for rep in range(2):       # a warm-up pass, a timed pass
+            for k in count:
+                count[k] = 0
+            calls0 = getattr(be, "frontend_calls", 0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        rec = {"route": route, "mode": "tokens", "commit": commit, "normalize": args.normalize, "clips": len(names),
+               "vocab": args.vocab, "warmup_s": round(times[0], 4), "timed_s": round(times[1], 4),
+               "native_frontend_calls": count["native"] + getattr(be, "frontend_calls", 0) - calls0,
+               "d2h_copies": count["d2h_copies"], "d2h_bytes": count["d2h_bytes"]}
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+    if len(routes) == 2:
+        a = {p.name: p.read_bytes() for p in Path(cfg.dest_tokenized_path, "train").glob("*.npy")}
+        b = {p.name: p.read_bytes() for p in direct.glob("*.npy")}
+        rec = {"route": "cross_check", "mode": "tokens", "commit": commit, "same_bytes": a == b, "files": len(a)}
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+        assert a == b, "the two routes wrote different token files"
+    return lines
 
 
 if __name__ == "__main__":
