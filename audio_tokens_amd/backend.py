@@ -288,20 +288,24 @@ class HipBackend(HostHelpers):
         return ev
 
     # -- operators ---------------------------------------------------------------------------
-    def logmel(self, wave, sample_rate=22050, n_fft=512, hop=128, n_mels=64, fb=None,
-               frame_major=False, l2norm=False, out=None) -> torch.Tensor:
-        """wave [n_clips, L] (or [L]) -> [n_clips, n_mels, T], or [n_clips*T, n_mels] if frame_major.
-        n_fft: any even size from 64 to 4096 (odd sizes raise NativeError: torch counts their frames differently);
-        1 <= hop <= n_fft, L > n_fft/2."""
+    def _logmel_args(self, wave, n_fft, hop, n_mels, fb):
+        """What logmel and logmel_minmax share -> (wave [n_clips, L] on the device, n_clips, L, T, fb on the device)."""
         wave = self._f32(wave)
         if wave.dim() == 1:
             wave = wave.unsqueeze(0)
         assert wave.dim() == 2
         n_clips, L = wave.shape
-        T = self.num_frames(L, hop)
         fbt = self._f32(fb) if fb is not None else None
         if fbt is not None:
             assert tuple(fbt.shape) == (n_fft // 2 + 1, n_mels), "fb must be [n_fft/2+1, n_mels]"
+        return wave, n_clips, L, self.num_frames(L, hop), fbt
+
+    def logmel(self, wave, sample_rate=22050, n_fft=512, hop=128, n_mels=64, fb=None,
+               frame_major=False, l2norm=False, out=None) -> torch.Tensor:
+        """wave [n_clips, L] (or [L]) -> [n_clips, n_mels, T], or [n_clips*T, n_mels] if frame_major.
+        n_fft: any even size from 64 to 4096 (odd sizes raise NativeError: torch counts their frames differently);
+        1 <= hop <= n_fft, L > n_fft/2."""
+        wave, n_clips, L, T, fbt = self._logmel_args(wave, n_fft, hop, n_mels, fb)
         shape = (n_clips * T, n_mels) if frame_major else (n_clips, n_mels, T)
         if out is None:
             out = self.empty(shape)
@@ -324,12 +328,7 @@ class HipBackend(HostHelpers):
     def logmel_minmax(self, wave, sample_rate=22050, n_fft=512, hop=128, n_mels=64, fb=None) -> torch.Tensor:
         """wave [n_clips, L] -> [n_clips, n_mels, T]: logmel() followed by minmax_scale_clips(), one call; the extremes are
         collected by the log-mel kernel (at_logmel_minmax_f32), so the scaling is a single pass."""
-        wave = self._f32(wave)
-        if wave.dim() == 1:
-            wave = wave.unsqueeze(0)
-        n_clips, L = wave.shape
-        T = self.num_frames(L, hop)
-        fbt = self._f32(fb) if fb is not None else None
+        wave, n_clips, L, T, fbt = self._logmel_args(wave, n_fft, hop, n_mels, fb)
         out = self.empty((n_clips, n_mels, T))
         with torch.cuda.device(self.device):
             for c0 in range(0, n_clips, 65535):

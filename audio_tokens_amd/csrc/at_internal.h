@@ -341,12 +341,15 @@ __device__ __forceinline__ long reflect_index(long q, long L) {
     return q;
 }
 
-// logmel_any.hip: every even n_fft other than 512.  plan_or_null: the ragged form (at_logmel_ragged_f32) -- `wave` is
-// the intermediate buffer, the device plan says where every clip lies, clip_bad receives the per-clip flags,
-// ragged_frames is the plan's total; L and wave_stride are not used.
-int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, int64_t wave_stride, int sample_rate,
-                  int n_fft, int hop, int n_mels, const float* fb_user_dev, float* out, int frame_major,
-                  const at_frontend_clip* plan_or_null, int32_t* clip_bad, int64_t ragged_frames, hipStream_t stream);
+// logmel_any.hip: every even n_fft other than 512, over the clips of a map (logmel_clips.h: lmc::UniformClips or
+// lmc::PlanClips, the two instantiations) with n_frames output frames in all.
+namespace lmc {
+struct UniformClips;
+struct PlanClips;
+}
+template <typename Clips>
+int at_logmel_any(at_ctx* ctx, const Clips& clips, int64_t n_frames, int sample_rate, int n_fft, int hop, int n_mels,
+                  const float* fb_user_dev, float* out, int frame_major, hipStream_t stream);
 
 // assign.hip: the centroid image of the any-d sweep (tiles of 32 * na rows, features in chunks of 64, |c|^2 of a tile
 // behind its last chunk, +inf for rows >= k); at_chunked_image_tile_floats(d, na) floats per tile.  Used by knn.hip.

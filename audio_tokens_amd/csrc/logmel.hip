@@ -15,15 +15,19 @@
 // along the rows, even/odd untangling to the 257 power bins (logmel_core.h), then the mel
 // filterbank as a banded dot product per filter (only the non-zero taps), 10*log10, and a staged
 // coalesced store.  Algorithmic HBM traffic: hop*4 bytes in + n_mels*4 bytes out per frame.
+//
+// Whose clip a block is, and where that clip lies, is the clip map's business (logmel_clips.h): the uniform batch of
+// at_logmel_f32 and the plan of at_logmel_ragged_f32 are two instantiations of the same kernel, of the same min-max
+// passes and of the same host driver (logmel_drive), which also sends every other n_fft to logmel_any.hip.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <type_traits>
 #include <vector>
 
 #include "at_internal.h"
 #include "l2norm_core.h"
+#include "logmel_clips.h"
 #include "logmel_core.h"
 #include "logmel_tables.h"
 
@@ -39,12 +43,10 @@ constexpr int TAB_WIN = 0, TAB_TW256 = 512, TAB_TW512 = 1024, TAB_FLOATS = 1536;
 // opposite halves of the banks.
 constexpr int FRAME_STRIDE = FRAME_LDS_FLOATS + 32;
 
-struct LogmelParams {
-    const float* wave;
-    long n_clips, L, wave_stride;
-    int hop, T, n_mels, fpb;
+// What the kernel needs beside the clips: the tables, the block geometry and where the output goes.
+struct LogmelCommon {
+    int hop, n_mels, fpb;
     long n_blocks;          // (clip, block of fpb frames) pairs, walked by persistent workgroups
-    int blocks_per_clip;
     const float* tabs;      // TAB_FLOATS floats: window, W256 twiddles, W512 twiddles
     const int* fb_start;    // [n_mels]
     const int* fb_len;      // [n_mels]
@@ -57,59 +59,14 @@ struct LogmelParams {
     int frame_major, fuse_l2norm;
     int* bad;               // set to 1 when a frame's squared norm is not finite (fused unit rows only)
     unsigned* minmax;       // optional [n_clips][4]: ordered keys of the clip's smallest / largest dB value, a NaN flag
-                            // (at_logmel_minmax_f32: SpectrogramGenerator's normalize option without a reduction pass)
+                            // (the min-max entries: SpectrogramGenerator's normalize option without a reduction pass)
+};
+// Clips: the map from a block to its clip (logmel_clips.h)
+template <typename Clips>
+struct LogmelParams : LogmelCommon {
+    Clips clips;
 };
 
-// The ragged form (at_logmel_ragged_f32): the clips of an at_frontend_plan_host plan, each with its own length, frames
-// and place in the output.  `wave` is the intermediate buffer, n_blocks counts the blocks of all clips, and L,
-// wave_stride, T and blocks_per_clip are not used.
-struct RaggedLogmelParams : LogmelParams {
-    const at_frontend_clip* plan;
-    int* clip_bad;          // [n_clips]: set where a value stored for the clip is not finite
-};
-
-// One block of fpb frames: whose it is, and that clip's geometry.
-struct BlockOf {
-    long clip;
-    int t0, T;              // first frame of the block, frames of the clip
-    const float* w;         // the clip
-    long L;
-    float* out_mel;         // the clip's [n_mels][T] block / its first [n_mels] row
-    float* out_frames;
-};
-// uniform: blocks_per_clip blocks per clip
-__device__ __forceinline__ BlockOf block_of(const LogmelParams& p, long blk) {
-    BlockOf b;
-    b.clip = blk / p.blocks_per_clip;
-    b.t0 = (int)(blk - b.clip * p.blocks_per_clip) * p.fpb;
-    b.T = p.T;
-    b.w = p.wave + b.clip * p.wave_stride;
-    b.L = p.L;
-    b.out_mel = p.out + (long)b.clip * p.n_mels * p.T;
-    b.out_frames = p.out + (long)b.clip * p.T * p.n_mels;
-    return b;
-}
-// ragged: the clip whose block prefix is the last one <= blk (a clip without frames shares its prefix with the clip
-// behind it and is never found)
-__device__ __forceinline__ BlockOf block_of(const RaggedLogmelParams& p, long blk) {
-    const bool b32 = p.fpb == 32;
-    long lo = 0, hi = p.n_clips;
-    while (hi - lo > 1) {
-        const long mid = (lo + hi) >> 1;
-        if ((b32 ? p.plan[mid].first_block32 : p.plan[mid].first_block16) <= blk) lo = mid;
-        else hi = mid;
-    }
-    const at_frontend_clip& c = p.plan[lo];
-    BlockOf b;
-    b.clip = lo;
-    b.t0 = (int)(blk - (b32 ? c.first_block32 : c.first_block16)) * p.fpb;
-    b.T = c.n_frames;
-    b.w = p.wave + c.mono_offset;
-    b.L = c.out_length;
-    b.out_mel = p.out + c.first_frame * p.n_mels;
-    b.out_frames = b.out_mel;
-    return b;
-}
 __device__ __forceinline__ int not_finite(float v) { return !(__builtin_fabsf(v) < __builtin_inff()); }
 
 // floats as unsigned keys that order the same way (atomicMin / atomicMax on them)
@@ -131,52 +88,49 @@ __global__ void __launch_bounds__(256) minmax_init_kernel(unsigned* __restrict__
     }
 }
 
-// (spec - min) / (max - min) per clip with the extremes the log-mel kernel collected: two subtractions and one
-// IEEE division per element, torch's bits (processors/spectrogram_generator.py:129-131); a NaN anywhere in the clip
-// makes the whole clip NaN, as torch.min / max propagate it.
-__global__ void __launch_bounds__(256) minmax_apply_kernel(float* __restrict__ x, long clip_elems, const unsigned* __restrict__ mm) {
-    const long clip = blockIdx.y;
-    float lo = key_to_float(mm[4 * clip]), hi = key_to_float(mm[4 * clip + 1]);
-    if (mm[4 * clip + 2]) lo = hi = __builtin_nanf("");
-    const float range = hi - lo;
-    float* p = x + (size_t)clip * clip_elems;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < clip_elems; e += (long)gridDim.x * 256) p[e] = __fdiv_rn(p[e] - lo, range);
+// A wavefront's (lo, hi, nan) of values of one clip, folded into the clip's record `rec` (minmax_init_kernel's): one
+// pair of atomics per call.  Lanes that saw nothing bring +inf / -inf / 0.
+__device__ __forceinline__ void commit_extremes(unsigned* rec, float lo, float hi, int nan, int lane) {
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = __builtin_fminf(lo, __shfl_xor(lo, off));
+        hi = __builtin_fmaxf(hi, __shfl_xor(hi, off));
+        nan |= __shfl_xor(nan, off);
+    }
+    if (lane == 0) {
+        if (lo <= hi) {
+            atomicMin(&rec[0], ordered_key(lo));
+            atomicMax(&rec[1], ordered_key(hi));
+        }
+        if (nan) atomicOr(&rec[2], 1u);
+    }
 }
 
-// ---- the ragged forms (at_logmel_ragged_minmax_f32) ---------------------------------------------------------------------
-// The output of a plan is one flat run of floats in either layout: clip i owns [first_frame, first_frame + n_frames) x
-// n_mels of it.  A wavefront takes MM_CHUNK consecutive floats at a time and walks the pieces of clips inside them: the
-// clip of a piece is the one whose first_frame is the last one <= the piece's first frame (binary search, as the
-// per-frame kernels do; a clip without frames shares its prefix with the clip behind it and is never found), the
-// piece ends where the clip or the chunk does.  Everything that decides the walk is the same in all 64 lanes.
+// ---- the passes over a finished output (the min-max entries) -----------------------------------------------------------
+// The output of either clip map is one flat run of floats in either layout: a clip owns [base, base + T) x n_mels of
+// it.  A wavefront takes MM_CHUNK consecutive floats at a time and walks the pieces of clips inside them: a piece
+// belongs to the clip that owns its first frame and ends where that clip or the chunk does (lmc::clip_end).
+// Everything that decides the walk is the same in all 64 lanes.
 constexpr int MM_CHUNK = 4096;
-struct RaggedMinmaxParams {
+template <typename Clips>
+struct MinmaxParams {
     float* x;                       // [n_frames][n_mels] floats, clip after clip
     long total;                     // n_frames * n_mels
     int n_mels, vec;                // vec: n_mels % 4 == 0 and x 16-byte aligned, so every piece is whole aligned quads
-    const at_frontend_clip* plan;
-    long n_clips;
+    Clips clips;
     unsigned* mm;                   // [n_clips][4] records, as minmax_init_kernel leaves them
-    int* clip_bad;                  // [n_clips] (the scaling pass)
 };
-template <typename Body>
-__device__ __forceinline__ void ragged_pieces(const RaggedMinmaxParams& p, Body body) {
+template <typename Clips, typename Body>
+__device__ __forceinline__ void clip_pieces(const MinmaxParams<Clips>& p, Body body) {
     const int lane = threadIdx.x & 63;
     const long wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
     const long n_waves = (long)gridDim.x * (blockDim.x >> 6);
     for (long a = wave * MM_CHUNK; a < p.total; a += n_waves * MM_CHUNK) {
         const long b = min(p.total, a + MM_CHUNK);
         for (long s = a; s < b;) {
-            const long g = s / p.n_mels;
-            long lo = 0, hi = p.n_clips;
-            while (hi - lo > 1) {
-                const long mid = (lo + hi) >> 1;
-                if (p.plan[mid].first_frame <= g) lo = mid;
-                else hi = mid;
-            }
-            const long end = min(b, (p.plan[lo].first_frame + p.plan[lo].n_frames) * p.n_mels);
+            long clip;
+            const long end = min(b, lmc::clip_end(p.clips, s / p.n_mels, &clip) * p.n_mels);
             if (end <= s) return;   // (a plan that does not cover the output: never loop on it)
-            body(lo, s, end, lane);
+            body(clip, s, end, lane);
             s = end;
         }
     }
@@ -184,9 +138,10 @@ __device__ __forceinline__ void ragged_pieces(const RaggedMinmaxParams& p, Body 
 
 // The reduction pass behind the transforms that do not collect the extremes themselves (every n_fft but 512): the same
 // records, ordered keys and NaN flag as the tuned kernel leaves, one pair of atomics per piece.  4 B read per value.
-__global__ void __launch_bounds__(256) minmax_scale_kernel_ragged_extremes(RaggedMinmaxParams p) {
+template <typename Clips>
+__global__ void __launch_bounds__(256) minmax_extremes_kernel(MinmaxParams<Clips> p) {
     typedef float f4 __attribute__((ext_vector_type(4)));
-    ragged_pieces(p, [&](long clip, long s, long end, int lane) {
+    clip_pieces(p, [&](long clip, long s, long end, int lane) {
         float lo = __builtin_inff(), hi = -__builtin_inff();
         int nan = 0;
         if (p.vec) {
@@ -208,28 +163,20 @@ __global__ void __launch_bounds__(256) minmax_scale_kernel_ragged_extremes(Ragge
                 hi = __builtin_fmaxf(hi, v);
             }
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            lo = __builtin_fminf(lo, __shfl_xor(lo, off));
-            hi = __builtin_fmaxf(hi, __shfl_xor(hi, off));
-            nan |= __shfl_xor(nan, off);
-        }
-        if (lane == 0) {
-            if (lo <= hi) {
-                atomicMin(&p.mm[4 * clip], ordered_key(lo));
-                atomicMax(&p.mm[4 * clip + 1], ordered_key(hi));
-            }
-            if (nan) atomicOr(&p.mm[4 * clip + 2], 1u);
-        }
+        commit_extremes(p.mm + 4 * clip, lo, hi, nan, lane);
     });
 }
 
-// minmax_apply_kernel for the clips of a plan, either layout: the same two subtractions and one IEEE division per value.
-// A clip is flagged where a value stored for it is not finite -- the reference checks for NaN / Inf after normalising
+// (spec - min) / (max - min) per clip with the extremes collected before, either layout: two subtractions and one
+// IEEE division per value, torch's bits (processors/spectrogram_generator.py:129-131); a NaN anywhere in the clip
+// makes the whole clip NaN, as torch.min / max propagate it.  A map with flags has a clip flagged where a value stored
+// for it is not finite -- the reference checks for NaN / Inf after normalising
 // (processors/spectrogram_generator.py:107-110), so a constant clip (0 / 0) is skipped like one with a NaN sample.
 // 8 B per value.
-__global__ void __launch_bounds__(256) minmax_apply_kernel_ragged(RaggedMinmaxParams p) {
+template <typename Clips>
+__global__ void __launch_bounds__(256) minmax_scale_pieces_kernel(MinmaxParams<Clips> p) {
     typedef float f4 __attribute__((ext_vector_type(4)));
-    ragged_pieces(p, [&](long clip, long s, long end, int lane) {
+    clip_pieces(p, [&](long clip, long s, long end, int lane) {
         float lo = key_to_float(p.mm[4 * clip]), hi = key_to_float(p.mm[4 * clip + 1]);
         if (p.mm[4 * clip + 2]) lo = hi = __builtin_nanf("");
         const float range = hi - lo;
@@ -252,15 +199,16 @@ __global__ void __launch_bounds__(256) minmax_apply_kernel_ragged(RaggedMinmaxPa
                 p.x[e] = v;
             }
         }
-        if (flagged) p.clip_bad[clip] = 1;   // (every writer stores the same value)
+        if constexpr (Clips::has_flags)
+            if (flagged) p.clips.flags[clip] = 1;   // (every writer stores the same value)
     });
 }
 
 // PF: the next block's samples are prefetched through registers (needs a block of at most PREFETCH_REGS x WG x 4
 // samples); otherwise they are staged at the top of the block.
-// RG: the ragged form.
-template <bool PF, bool RG = false>
-__global__ void __launch_bounds__(WG, 2) logmel_kernel(typename std::conditional<RG, RaggedLogmelParams, LogmelParams>::type p) {
+// Clips: which clip a block belongs to (logmel_clips.h).
+template <bool PF, typename Clips>
+__global__ void __launch_bounds__(WG, 2) logmel_kernel(LogmelParams<Clips> p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l16 = lane & 15, grp = lane >> 4;
@@ -308,9 +256,9 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(typename std::conditional
     const int nsamp4 = (nsamp + 3) >> 2;
     f4 pre[PREFETCH_REGS];
     auto prefetch = [&](long blk) {
-        const BlockOf at = block_of(p, blk);
+        const lmc::ClipAt at = p.clips.by_block(blk, p.fpb);
         const float* w = at.w;
-        const long s0 = (long)at.t0 * p.hop - NFFT / 2;
+        const long s0 = (long)at.t * p.hop - NFFT / 2;
         const bool fast = s0 >= 0 && s0 + 4L * nsamp4 <= at.L && ((reinterpret_cast<uintptr_t>(w + s0) & 15) == 0);
         if (fast) {
             const f4* src = reinterpret_cast<const f4*>(w + s0);
@@ -335,9 +283,9 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(typename std::conditional
     if constexpr (PF)
         if ((long)blockIdx.x < p.n_blocks) prefetch(blockIdx.x);
     for (long blk = blockIdx.x; blk < p.n_blocks; blk += gridDim.x) {
-        const BlockOf at = block_of(p, blk);
+        const lmc::ClipAt at = p.clips.by_block(blk, p.fpb);
         const long clip = at.clip;
-        const int t0 = at.t0;
+        const int t0 = at.t;
         if constexpr (PF) {
 #pragma unroll
             for (int j = 0; j < PREFETCH_REGS; j++) {
@@ -382,7 +330,7 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(typename std::conditional
         __syncthreads();
 
         const int nf = min(p.fpb, at.T - t0);  // frames of this block that exist
-        int flagged = 0;                      // (ragged) a value stored by this lane is not finite
+        int flagged = 0;                      // (a map with flags) a value stored by this lane is not finite
         if (p.minmax) {   // the clip's extremes, from the staged block: one pair of atomics per workgroup and block
             float lo = __builtin_inff(), hi = -__builtin_inff();
             int nan = 0;
@@ -393,18 +341,7 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(typename std::conditional
                 lo = __builtin_fminf(lo, v);
                 hi = __builtin_fmaxf(hi, v);
             }
-            for (int off = 32; off > 0; off >>= 1) {
-                lo = __builtin_fminf(lo, __shfl_xor(lo, off));
-                hi = __builtin_fmaxf(hi, __shfl_xor(hi, off));
-                nan |= __shfl_xor(nan, off);
-            }
-            if (lane == 0) {
-                if (lo <= hi) {
-                    atomicMin(&p.minmax[4 * clip], ordered_key(lo));
-                    atomicMax(&p.minmax[4 * clip + 1], ordered_key(hi));
-                }
-                if (nan) atomicOr(&p.minmax[4 * clip + 2], 1u);
-            }
+            commit_extremes(p.minmax + 4 * clip, lo, hi, nan, lane);
         }
         if (p.frame_major) {
             float* den = ostage + p.fpb * opitch;
@@ -420,7 +357,7 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(typename std::conditional
                 }
                 __syncthreads();
             }
-            float* dst = at.out_frames + (long)t0 * p.n_mels;
+            float* dst = p.out + (at.base + t0) * p.n_mels;
             if ((p.n_mels & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {   // 16 bytes per lane
                 const int mq = p.n_mels >> 2, total4 = nf * mq;
                 for (int e4 = tid; e4 < total4; e4 += WG) {
@@ -432,7 +369,7 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(typename std::conditional
 #pragma unroll
                         for (int e = 0; e < 4; e++) v[e] = l2n::divide(v[e], dn);
                     }
-                    if constexpr (RG) flagged |= not_finite(v[0]) | not_finite(v[1]) | not_finite(v[2]) | not_finite(v[3]);
+                    if constexpr (Clips::has_flags) flagged |= not_finite(v[0]) | not_finite(v[1]) | not_finite(v[2]) | not_finite(v[3]);
                     reinterpret_cast<f4*>(dst)[e4] = v;
                 }
             } else {
@@ -441,24 +378,24 @@ __global__ void __launch_bounds__(WG, 2) logmel_kernel(typename std::conditional
                     const int f = e / p.n_mels, m = e - f * p.n_mels;
                     float v = ostage[f * opitch + m];
                     if (p.fuse_l2norm) v = l2n::divide(v, den[f]);
-                    if constexpr (RG) flagged |= not_finite(v);
+                    if constexpr (Clips::has_flags) flagged |= not_finite(v);
                     dst[e] = v;
                 }
             }
         } else {
-            float* dst = at.out_mel + t0;
+            float* dst = p.out + at.base * p.n_mels + t0;
             const int total = p.n_mels * p.fpb;
             for (int e = tid; e < total; e += WG) {
                 const int m = e / p.fpb, f = e - m * p.fpb;
                 if (f < nf) {
                     const float v = ostage[f * opitch + m];
-                    if constexpr (RG) flagged |= not_finite(v);
+                    if constexpr (Clips::has_flags) flagged |= not_finite(v);
                     dst[(long)m * at.T + f] = v;
                 }
             }
         }
-        if constexpr (RG)
-            if (flagged) p.clip_bad[clip] = 1;   // (every writer stores the same value)
+        if constexpr (Clips::has_flags)
+            if (flagged) p.clips.flags[clip] = 1;   // (every writer stores the same value)
         // (no barrier here: the next block's samples go to `samp`, which nobody reads any more, and its
         // barrier above comes before anybody writes the staged output again)
     }
@@ -546,14 +483,14 @@ int at_logmel_resident(at_ctx* ctx, int slot, at_logmel_tables* rec, const at_lo
     return AT_OK;
 }
 
-// What the uniform and the ragged launch of the tuned kernel share: argument checks are the caller's; this fills the
-// tables, the frames per block, the LDS size and which of the two kernels (prefetch or not) applies.
+// The tuned kernel's launch, whatever the clips: this fills the tables, the frames per block, the LDS size and which
+// of the two kernels (prefetch or not) applies.
 struct Setup512 {
     size_t lds;
     bool pf, fuse_here;
 };
 static int setup_512(at_ctx* ctx, int sample_rate, int hop, int n_mels, const float* fb_or_null, int fuse_l2norm,
-                     hipStream_t stream, LogmelParams& p, Setup512& su) {
+                     hipStream_t stream, LogmelCommon& p, Setup512& su) {
     const at_logmel_tables key{sample_rate, NFFT, n_mels, hop, /* form */ 0};
     const lmt::BlobLayout lay = lmt::blob_layout(TAB_FLOATS, n_mels);
     // (capacity: the worst case, every bin of every filter and its quad padding)
@@ -599,176 +536,174 @@ static int check_logmel_args(const char* who, at_ctx* ctx, int n_fft, int hop, i
     return AT_OK;
 }
 
-static int logmel_impl(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L,
-                       int64_t wave_stride, int sample_rate, int n_fft, int hop, int n_mels,
-                       const float* fb_or_null, float* out, int layout, int fuse_l2norm,
-                       unsigned* minmax, hipStream_t stream) {
-    int rc = check_logmel_args("at_logmel_f32", ctx, n_fft, hop, n_mels, layout, fuse_l2norm);
-    if (rc) return rc;
-    AT_REQUIRE(n_clips >= 0 && n_clips <= 65535 * 1024L, "at_logmel_f32: n_clips out of range");
-    AT_REQUIRE(L > n_fft / 2, "at_logmel_f32: clip length %lld must exceed n_fft/2 (reflect padding)", (long long)L);
-    AT_REQUIRE(wave_stride >= L, "at_logmel_f32: wave_stride < L");
-    if (n_clips == 0) return AT_OK;
-    AT_REQUIRE(wave && out, "at_logmel_f32: null pointer");
-    AT_HIP(hipSetDevice(ctx->device));
-    if (n_fft != NFFT) {   // the general form (logmel_any.hip); unit rows by the stand-alone kernel behind it
-        AT_REQUIRE(at_num_frames(L, hop) < (1LL << 31), "at_logmel_f32: too many frames per clip");
-        rc = at_logmel_any(ctx, wave, n_clips, L, wave_stride, sample_rate, n_fft, hop, n_mels, fb_or_null, out,
-                           layout == AT_LAYOUT_FRAME_MAJOR, nullptr, nullptr, 0, stream);
-        if (rc) return rc;
-        if (fuse_l2norm) {
-            int* bad = at_row_flag(ctx, stream);
-            if (!bad) return AT_E_NOMEM;
-            return at_l2norm_rows_flagged(ctx, out, n_clips * at_num_frames(L, hop), n_mels, out, bad, stream);
-        }
-        return AT_OK;
-    }
+// One call of the family, as its entry hands it to the driver.
+struct LogmelCall {
+    const char* who;
+    at_ctx* ctx;
+    int sample_rate, n_fft, hop, n_mels;
+    const float* fb_or_null;
+    float* out;
+    int layout, fuse_l2norm;
+    bool minmax;            // every clip becomes (spec - min) / (max - min) through the WS_LOGMEL_MINMAX records
+    hipStream_t stream;
+};
+// The clips of a call, as its entry's `prepare` leaves them: the map and its totals (n_frames = 0: nothing to do).
+template <typename Clips>
+struct ClipSet {
+    Clips clips;
+    int64_t n_clips, n_frames, n_blocks16, n_blocks32;
+};
 
-    LogmelParams p;
-    Setup512 su;
-    rc = setup_512(ctx, sample_rate, hop, n_mels, fb_or_null, fuse_l2norm, stream, p, su);
+// Every entry of the family: the checks all share, then the entry's own (`prepare`, which builds the clip map), then
+// n_fft = 512 on the tuned kernel or any other size on the general form (logmel_any.hip) over the same map.
+// minmax: the records are cleared first; the tuned kernel collects every clip's extremes while a block is still in
+// LDS, keyed by the block's clip, every other size is followed by a reduction pass over its output; then the scaling
+// pass, which sets the clips' flags where the map has them (the kernel's own unit rows stay off: the rows are scaled
+// first).  Last the unit rows the kernel did not fuse, by the stand-alone kernel, in place.  The clips' flags, set from
+// the dB values (or the scaled ones), hold for the unit rows: a NaN or Inf in a row makes the row NaN, and a finite
+// row stays finite.
+template <typename Clips, typename Prepare>
+static int logmel_drive(const LogmelCall& c, Prepare prepare) {
+    int rc = check_logmel_args(c.who, c.ctx, c.n_fft, c.hop, c.n_mels, c.layout, c.fuse_l2norm);
     if (rc) return rc;
-    const int64_t T = at_num_frames(L, hop);
-    AT_REQUIRE(T < (1LL << 31), "at_logmel_f32: too many frames per clip");
-    p.wave = wave; p.n_clips = n_clips; p.L = L; p.wave_stride = wave_stride;
-    p.T = (int)T;
-    p.out = out; p.frame_major = layout == AT_LAYOUT_FRAME_MAJOR;
-    p.minmax = minmax;
-    AT_RAISE_LDS(ctx, logmel_kernel<true>, su.lds);
-    AT_RAISE_LDS(ctx, logmel_kernel<false>, su.lds);
-    p.blocks_per_clip = (int)((T + p.fpb - 1) / p.fpb);
-    p.n_blocks = (long)p.blocks_per_clip * n_clips;
-    // persistent workgroups: two per CU (what the LDS footprint allows), each walking a strided share
-    // of the blocks with its window / twiddle tables in registers
-    long grid = 2L * ctx->n_cus;
-    if (grid > p.n_blocks) grid = p.n_blocks;
-    if (su.pf) AT_LAUNCH(logmel_kernel<true>, dim3((unsigned)grid), dim3(WG), su.lds, stream, p);
-    else AT_LAUNCH(logmel_kernel<false>, dim3((unsigned)grid), dim3(WG), su.lds, stream, p);
-    if (fuse_l2norm && !su.fuse_here) return at_l2norm_rows_flagged(ctx, out, n_clips * T, n_mels, out, p.bad, stream);
-    return AT_OK;
-}
-
-// at_logmel_f32 for the clips of an at_frontend_plan_host plan, one launch (include/audio_tokens_amd.h).  The same
-// kernels over the same tables as the uniform call; only where a block or frame finds its clip differs.
-// minmax (at_logmel_ragged_minmax_f32): every clip becomes (spec - min) / (max - min) before the unit rows, if any.
-// n_fft = 512: the tuned kernel collects every clip's extremes while a block is still in LDS, keyed by the block's
-// clip; every other size: the transform as it is, then a reduction pass over its output.  Then the scaling pass, which
-// sets the clips' flags, and -- fuse_l2norm -- the stand-alone unit rows over the scaled rows, in place (the kernel's
-// own unit rows stay off: the rows are scaled first).
-static int logmel_ragged_impl(const char* who, at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev,
-                              int64_t n_clips, const at_frontend_totals* totals, int sample_rate, int n_fft, int hop,
-                              int n_mels, const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad,
-                              bool minmax, hipStream_t stream) {
-    int rc = check_logmel_args(who, ctx, n_fft, hop, n_mels, layout, fuse_l2norm);
-    if (rc) return rc;
-    AT_REQUIRE(n_clips >= 0 && n_clips < (1LL << 31), "%s: n_clips out of range", who);
-    if (n_clips == 0) return AT_OK;
-    AT_REQUIRE(totals && plan_dev && bad, "%s: null pointer", who);
-    AT_REQUIRE(totals->n_frames >= 0 && totals->n_blocks16 >= 0 && totals->n_blocks32 >= 0 &&
-                   totals->n_blocks32 <= totals->n_blocks16 && totals->n_blocks16 <= totals->n_frames,
-               "%s: bad totals", who);
-    AT_HIP(hipSetDevice(ctx->device));
-    AT_HIP(hipMemsetAsync(bad, 0, (size_t)n_clips * sizeof(int32_t), stream));
-    if (totals->n_frames == 0) return AT_OK;   // every clip too short
-    AT_REQUIRE(mono && out, "%s: null pointer", who);
-    RaggedMinmaxParams mp{};
+    AT_HIP(hipSetDevice(c.ctx->device));
+    ClipSet<Clips> cs{};
+    rc = prepare(cs);
+    if (rc || cs.n_frames == 0) return rc;
+    AT_REQUIRE(cs.clips.wave && c.out, "%s: null pointer", c.who);
+    const int frame_major = c.layout == AT_LAYOUT_FRAME_MAJOR;
+    MinmaxParams<Clips> mp{};
     long mgrid = 0;
-    if (minmax) {
-        mp.mm = static_cast<unsigned*>(at_ws(ctx, WS_LOGMEL_MINMAX, (size_t)n_clips * 16, stream));
+    if (c.minmax) {
+        mp.mm = static_cast<unsigned*>(at_ws(c.ctx, WS_LOGMEL_MINMAX, (size_t)cs.n_clips * 16, c.stream));
         if (!mp.mm) return AT_E_NOMEM;
-        AT_LAUNCH(minmax_init_kernel, dim3((unsigned)((n_clips + 255) / 256)), dim3(256), 0, stream, mp.mm, (long)n_clips);
-        mp.x = out; mp.total = (long)totals->n_frames * n_mels; mp.n_mels = n_mels;
-        mp.vec = (n_mels & 3) == 0 && at_aligned16(out);
-        mp.plan = plan_dev; mp.n_clips = n_clips; mp.clip_bad = bad;
+        AT_LAUNCH(minmax_init_kernel, dim3((unsigned)((cs.n_clips + 255) / 256)), dim3(256), 0, c.stream, mp.mm, (long)cs.n_clips);
+        mp.x = c.out; mp.total = (long)cs.n_frames * c.n_mels; mp.n_mels = c.n_mels;
+        mp.vec = (c.n_mels & 3) == 0 && at_aligned16(c.out);
+        mp.clips = cs.clips;
         // one wavefront per MM_CHUNK floats, at most eight workgroups per CU walking the rest
         mgrid = ((mp.total + MM_CHUNK - 1) / MM_CHUNK + 3) / 4;
-        if (mgrid > 8L * ctx->n_cus) mgrid = 8L * ctx->n_cus;
+        if (mgrid > 8L * c.ctx->n_cus) mgrid = 8L * c.ctx->n_cus;
     }
     bool rows_done = false;   // the unit rows came out of the log-mel kernel
-    if (n_fft != NFFT) {
-        rc = at_logmel_any(ctx, mono, n_clips, 0, 0, sample_rate, n_fft, hop, n_mels, fb_or_null, out,
-                           layout == AT_LAYOUT_FRAME_MAJOR, plan_dev, bad, totals->n_frames, stream);
+    if (c.n_fft != NFFT) {
+        rc = at_logmel_any(c.ctx, cs.clips, cs.n_frames, c.sample_rate, c.n_fft, c.hop, c.n_mels, c.fb_or_null, c.out,
+                           frame_major, c.stream);
         if (rc) return rc;
-        if (minmax) AT_LAUNCH(minmax_scale_kernel_ragged_extremes, dim3((unsigned)mgrid), dim3(256), 0, stream, mp);
+        if (c.minmax) AT_LAUNCH(minmax_extremes_kernel<Clips>, dim3((unsigned)mgrid), dim3(256), 0, c.stream, mp);
     } else {
-        RaggedLogmelParams p;
+        LogmelParams<Clips> p;
         Setup512 su;
-        rc = setup_512(ctx, sample_rate, hop, n_mels, fb_or_null, minmax ? 0 : fuse_l2norm, stream, p, su);
+        rc = setup_512(c.ctx, c.sample_rate, c.hop, c.n_mels, c.fb_or_null, c.minmax ? 0 : c.fuse_l2norm, c.stream, p, su);
         if (rc) return rc;
-        p.wave = mono; p.n_clips = n_clips; p.L = 0; p.wave_stride = 0; p.T = 0; p.blocks_per_clip = 0;
-        p.out = out; p.frame_major = layout == AT_LAYOUT_FRAME_MAJOR;
+        p.clips = cs.clips;
+        p.out = c.out; p.frame_major = frame_major;
         p.minmax = mp.mm;
-        p.plan = plan_dev; p.clip_bad = bad;
-        p.n_blocks = (long)(p.fpb == 32 ? totals->n_blocks32 : totals->n_blocks16);
-        AT_RAISE_LDS(ctx, (logmel_kernel<true, true>), su.lds);
-        AT_RAISE_LDS(ctx, (logmel_kernel<false, true>), su.lds);
-        long grid = 2L * ctx->n_cus;
+        p.n_blocks = (long)(p.fpb == 32 ? cs.n_blocks32 : cs.n_blocks16);
+        AT_RAISE_LDS(c.ctx, (logmel_kernel<true, Clips>), su.lds);
+        AT_RAISE_LDS(c.ctx, (logmel_kernel<false, Clips>), su.lds);
+        // persistent workgroups: two per CU (what the LDS footprint allows), each walking a strided share
+        // of the blocks with its window / twiddle tables in registers
+        long grid = 2L * c.ctx->n_cus;
         if (grid > p.n_blocks) grid = p.n_blocks;
-        if (su.pf) AT_LAUNCH((logmel_kernel<true, true>), dim3((unsigned)grid), dim3(WG), su.lds, stream, p);
-        else AT_LAUNCH((logmel_kernel<false, true>), dim3((unsigned)grid), dim3(WG), su.lds, stream, p);
+        if (su.pf) AT_LAUNCH((logmel_kernel<true, Clips>), dim3((unsigned)grid), dim3(WG), su.lds, c.stream, p);
+        else AT_LAUNCH((logmel_kernel<false, Clips>), dim3((unsigned)grid), dim3(WG), su.lds, c.stream, p);
         rows_done = su.fuse_here;
     }
-    if (minmax) AT_LAUNCH(minmax_apply_kernel_ragged, dim3((unsigned)mgrid), dim3(256), 0, stream, mp);
-    // unit rows by the stand-alone kernel, in place.  The clips' flags, set from the dB values (or the scaled ones), hold
-    // for the unit rows: a NaN or Inf in a row makes the row NaN, and a finite row stays finite.
-    if (fuse_l2norm && !rows_done) {
-        int* flag = at_row_flag(ctx, stream);
+    if (c.minmax) AT_LAUNCH(minmax_scale_pieces_kernel<Clips>, dim3((unsigned)mgrid), dim3(256), 0, c.stream, mp);
+    if (c.fuse_l2norm && !rows_done) {
+        int* flag = at_row_flag(c.ctx, c.stream);
         if (!flag) return AT_E_NOMEM;
-        rc = at_l2norm_rows_flagged(ctx, out, totals->n_frames, n_mels, out, flag, stream);
+        rc = at_l2norm_rows_flagged(c.ctx, c.out, cs.n_frames, c.n_mels, c.out, flag, c.stream);
     }
     return rc;
+}
+
+// The uniform entries: n_clips rows of L samples.  minmax: n_fft = 512 only (at_logmel_minmax_f32).
+static int logmel_uniform(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, int64_t wave_stride, int sample_rate,
+                          int n_fft, int hop, int n_mels, const float* fb_or_null, float* out, int layout, int fuse_l2norm,
+                          bool minmax, hipStream_t stream) {
+    const LogmelCall c{"at_logmel_f32", ctx, sample_rate, n_fft, hop, n_mels, fb_or_null, out, layout, fuse_l2norm, minmax, stream};
+    return logmel_drive<lmc::UniformClips>(c, [&](ClipSet<lmc::UniformClips>& cs) -> int {
+        AT_REQUIRE(n_clips >= 0 && n_clips <= 65535 * 1024L, "at_logmel_f32: n_clips out of range");
+        AT_REQUIRE(L > n_fft / 2, "at_logmel_f32: clip length %lld must exceed n_fft/2 (reflect padding)", (long long)L);
+        AT_REQUIRE(wave_stride >= L, "at_logmel_f32: wave_stride < L");
+        if (n_clips == 0) return AT_OK;
+        const int64_t T = at_num_frames(L, hop);
+        AT_REQUIRE(T < (1LL << 31), "at_logmel_f32: too many frames per clip");
+        cs.clips = lmc::UniformClips{wave, L, wave_stride, (int)T};
+        cs.n_clips = n_clips;
+        cs.n_frames = n_clips * T;
+        cs.n_blocks16 = (T + 15) / 16 * n_clips;
+        cs.n_blocks32 = (T + 31) / 32 * n_clips;
+        return AT_OK;
+    });
+}
+
+// at_logmel_f32 for the clips of an at_frontend_plan_host plan, one launch (include/audio_tokens_amd.h): the same
+// kernels over the same tables as the uniform call, over the plan's map.
+static int logmel_ragged(const char* who, at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev, int64_t n_clips,
+                         const at_frontend_totals* totals, int sample_rate, int n_fft, int hop, int n_mels,
+                         const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad, bool minmax,
+                         hipStream_t stream) {
+    const LogmelCall c{who, ctx, sample_rate, n_fft, hop, n_mels, fb_or_null, out, layout, fuse_l2norm, minmax, stream};
+    return logmel_drive<lmc::PlanClips>(c, [&](ClipSet<lmc::PlanClips>& cs) -> int {
+        AT_REQUIRE(n_clips >= 0 && n_clips < (1LL << 31), "%s: n_clips out of range", who);
+        if (n_clips == 0) return AT_OK;
+        AT_REQUIRE(totals && plan_dev && bad, "%s: null pointer", who);
+        AT_REQUIRE(totals->n_frames >= 0 && totals->n_blocks16 >= 0 && totals->n_blocks32 >= 0 &&
+                       totals->n_blocks32 <= totals->n_blocks16 && totals->n_blocks16 <= totals->n_frames,
+                   "%s: bad totals", who);
+        AT_HIP(hipMemsetAsync(bad, 0, (size_t)n_clips * sizeof(int32_t), stream));
+        cs.clips = lmc::PlanClips{mono, plan_dev, (long)n_clips, bad};
+        cs.n_clips = n_clips;
+        cs.n_frames = totals->n_frames;   // (0: every clip too short)
+        cs.n_blocks16 = totals->n_blocks16;
+        cs.n_blocks32 = totals->n_blocks32;
+        return AT_OK;
+    });
 }
 
 extern "C" int at_logmel_ragged_f32(at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev, int64_t n_clips,
                                     const at_frontend_totals* totals, int sample_rate, int n_fft, int hop, int n_mels,
                                     const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad,
                                     void* stream_) {
-    return logmel_ragged_impl("at_logmel_ragged_f32", ctx, mono, plan_dev, n_clips, totals, sample_rate, n_fft, hop, n_mels,
-                              fb_or_null, out, layout, fuse_l2norm, bad, false, (hipStream_t)stream_);
+    return logmel_ragged("at_logmel_ragged_f32", ctx, mono, plan_dev, n_clips, totals, sample_rate, n_fft, hop, n_mels,
+                         fb_or_null, out, layout, fuse_l2norm, bad, false, (hipStream_t)stream_);
 }
 
+// every clip becomes (spec - min) / (max - min) before the unit rows, if any
 extern "C" int at_logmel_ragged_minmax_f32(at_ctx* ctx, const float* mono, const at_frontend_clip* plan_dev, int64_t n_clips,
                                            const at_frontend_totals* totals, int sample_rate, int n_fft, int hop, int n_mels,
                                            const float* fb_or_null, float* out, int layout, int fuse_l2norm, int32_t* bad,
                                            void* stream_) {
-    return logmel_ragged_impl("at_logmel_ragged_minmax_f32", ctx, mono, plan_dev, n_clips, totals, sample_rate, n_fft, hop,
-                              n_mels, fb_or_null, out, layout, fuse_l2norm, bad, true, (hipStream_t)stream_);
+    return logmel_ragged("at_logmel_ragged_minmax_f32", ctx, mono, plan_dev, n_clips, totals, sample_rate, n_fft, hop,
+                         n_mels, fb_or_null, out, layout, fuse_l2norm, bad, true, (hipStream_t)stream_);
 }
 
 extern "C" int at_logmel_f32(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L,
                              int64_t wave_stride, int sample_rate, int n_fft, int hop, int n_mels,
                              const float* fb_or_null, float* out, int layout, int fuse_l2norm,
                              void* stream_) {
-    return logmel_impl(ctx, wave, n_clips, L, wave_stride, sample_rate, n_fft, hop, n_mels, fb_or_null, out, layout,
-                       fuse_l2norm, nullptr, (hipStream_t)stream_);
+    return logmel_uniform(ctx, wave, n_clips, L, wave_stride, sample_rate, n_fft, hop, n_mels, fb_or_null, out, layout,
+                          fuse_l2norm, false, (hipStream_t)stream_);
 }
 
 // MelSpectrogram + AmplitudeToDB + normalize_spectrogram (processors/spectrogram_generator.py:123-131 with
 // config.normalize = True): the log-mel kernel collects every clip's smallest and largest dB value while the block it
 // has just computed is still in LDS, so the scaling is ONE pass over the spectrogram (8 B per value) instead of a
-// reduction pass plus a scaling pass (12 B).  Other n_fft than 512: the general log-mel kernel, then the two-pass form.
+// reduction pass plus a scaling pass (12 B).  Other n_fft than 512: the general log-mel kernel, then the two-pass form
+// that needs no scratch (l2norm.hip).
 extern "C" int at_logmel_minmax_f32(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, int64_t wave_stride,
                                     int sample_rate, int n_fft, int hop, int n_mels, const float* fb_or_null, float* out,
                                     int layout, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     AT_REQUIRE(ctx, "at_logmel_minmax_f32: ctx is null");
     if (n_clips == 0) return AT_OK;
-    unsigned* mm = nullptr;
-    if (n_fft == NFFT) {   // the fused form: the kernel collects the extremes
-        AT_REQUIRE(n_clips <= 65535, "at_logmel_minmax_f32: at most 65535 clips per call");
-        AT_HIP(hipSetDevice(ctx->device));
-        mm = static_cast<unsigned*>(at_ws(ctx, WS_LOGMEL_MINMAX, (size_t)n_clips * 16, stream));
-        if (!mm) return AT_E_NOMEM;
-        AT_LAUNCH(minmax_init_kernel, dim3((unsigned)((n_clips + 255) / 256)), dim3(256), 0, stream, mm, (long)n_clips);
-    }
-    int rc = logmel_impl(ctx, wave, n_clips, L, wave_stride, sample_rate, n_fft, hop, n_mels, fb_or_null, out, layout, 0, mm,
-                         stream);
-    if (rc) return rc;
-    const int64_t clip_elems = at_num_frames(L, hop) * n_mels;   // (logmel_impl has checked every argument by now)
-    if (!mm) return at_minmax_scale_clips_f32(ctx, out, n_clips, clip_elems, stream_);
-    int bx = (int)((clip_elems + 256 * 8 - 1) / (256 * 8));
-    if (bx < 1) bx = 1;
-    if (bx > 64) bx = 64;
-    AT_LAUNCH(minmax_apply_kernel, dim3((unsigned)bx, (unsigned)n_clips), dim3(256), 0, stream, out, (long)clip_elems, mm);
-    return AT_OK;
+    const bool fused = n_fft == NFFT;
+    AT_REQUIRE(!fused || n_clips <= 65535, "at_logmel_minmax_f32: at most 65535 clips per call");
+    const int rc = logmel_uniform(ctx, wave, n_clips, L, wave_stride, sample_rate, n_fft, hop, n_mels, fb_or_null, out, layout,
+                                  0, fused, (hipStream_t)stream_);
+    if (rc || fused) return rc;
+    // (logmel_uniform has checked every argument by now)
+    return at_minmax_scale_clips_f32(ctx, out, n_clips, at_num_frames(L, hop) * n_mels, stream_);
 }

@@ -10,6 +10,7 @@
 // memory, twiddle and window tables sit in LDS.  Then the same even/odd untangling to the M + 1 power bins, the banded
 // mel dot products, 10 log10.  Same arithmetic contract as the tuned kernel (fp32 throughout, |X|^2 as re^2 + im^2,
 // clamp at 1e-10), same tolerance against the CPU restatement (tests/test_gpu_ops.py::test_logmel_other_nfft).
+// Which clip a frame belongs to is the clip map's business (logmel_clips.h): every kernel here is a template on it.
 // The even sizes that are not powers of two (400, 480, 1000, ...) take logmel_mixed_kernel further down: run-time
 // radices from {8, 4, 2, 3, 5, 7} where M has no larger prime factor, Bluestein's chirp transform elsewhere
 // (logmel_mixed_core.h; tests/test_gpu_logmel_nfft.py).
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "at_internal.h"
+#include "logmel_clips.h"
 #include "logmel_mixed_core.h"
 #include "logmel_tables.h"
 
@@ -26,11 +28,9 @@ using namespace lmx;
 
 constexpr int WG = 256;
 
-struct AnyParams {
-    const float* wave;
-    long n_clips, L, wave_stride;
-    int n_fft, log2m, hop, T, n_mels;
-    long n_frames;           // n_clips * T
+struct AnyCommon {
+    int n_fft, log2m, hop, n_mels;
+    long n_frames;           // of all clips
     const float* win;        // n_fft
     const float* twm;        // M x (cos, -sin) of 2*pi*q/M
     const float* twn;        // M x (cos, -sin) of 2*pi*k/n_fft
@@ -40,48 +40,13 @@ struct AnyParams {
     const float* fb_wts;
     float* out;
     int frame_major;
-    // the ragged form (at_logmel_ragged_f32): n_frames counts the frames of all clips; L, wave_stride and T are not used
-    const at_frontend_clip* plan;
-    int* clip_bad;           // [n_clips]: set where a value stored for the clip is not finite
 };
-
-// One frame: whose it is, and that clip's geometry.
-struct FrameOf {
-    long clip;
-    int t, T;               // frame within the clip, frames of the clip
-    const float* w;         // the clip
-    long L;
-    long mel_base;          // offset of the clip's [n_mels][T] block in the mel-major output
+// Clips: the map from an output frame to its clip (logmel_clips.h)
+template <typename Clips>
+struct AnyParams : AnyCommon {
+    Clips clips;
 };
-template <bool RG>
-__device__ __forceinline__ FrameOf frame_of(const AnyParams& p, long g) {
-    FrameOf f;
-    if constexpr (RG) {
-        // the clip whose first frame is the last one <= g (a clip without frames shares its prefix with the clip
-        // behind it and is never found)
-        long lo = 0, hi = p.n_clips;
-        while (hi - lo > 1) {
-            const long mid = (lo + hi) >> 1;
-            if (p.plan[mid].first_frame <= g) lo = mid;
-            else hi = mid;
-        }
-        const at_frontend_clip& c = p.plan[lo];
-        f.clip = lo;
-        f.t = (int)(g - c.first_frame);
-        f.T = c.n_frames;
-        f.w = p.wave + c.mono_offset;
-        f.L = c.out_length;
-        f.mel_base = c.first_frame * p.n_mels;
-    } else {
-        f.clip = g / p.T;
-        f.t = (int)(g - f.clip * p.T);
-        f.T = p.T;
-        f.w = p.wave + f.clip * p.wave_stride;
-        f.L = p.L;
-        f.mel_base = f.clip * p.n_mels * p.T;
-    }
-    return f;
-}
+using lmc::ClipAt;
 
 // One Stockham pass of radix R over M points held by one wavefront: butterfly j (of M/R) takes the inputs
 // j + t*M/R, multiplies input t by W_(NS*R)^(k*t) with k = j mod NS (NS = product of the radices before this pass),
@@ -148,7 +113,7 @@ struct FrameSrc {
     const float* win;   // n_fft window values
     long s0, L;
     bool inner;         // no reflection anywhere in this frame
-    __device__ __forceinline__ FrameSrc(const AnyParams& p, const FrameOf& f, const float* win_)
+    __device__ __forceinline__ FrameSrc(const AnyCommon& p, const ClipAt& f, const float* win_)
         : w(f.w), win(win_), s0((long)f.t * p.hop - p.n_fft / 2), L(f.L) {
         inner = s0 >= 0 && s0 + p.n_fft <= L;
     }
@@ -174,8 +139,8 @@ __device__ __forceinline__ void untangle_frame(int lane, int M, const float* z, 
 }
 
 // banded mel dot products, 10 log10, store in either layout
-template <bool RG>
-__device__ __forceinline__ void mel_db_store(int lane, const AnyParams& p, const float* pw, long g, const FrameOf& f) {
+template <typename Clips>
+__device__ __forceinline__ void mel_db_store(int lane, const AnyParams<Clips>& p, const float* pw, long g, const ClipAt& f) {
     int flagged = 0;
     for (int m = lane; m < p.n_mels; m += 64) {
         const float* wt = p.fb_wts + p.fb_off[m];
@@ -183,17 +148,17 @@ __device__ __forceinline__ void mel_db_store(int lane, const AnyParams& p, const
         float acc = 0.0f;
         for (int q = 0; q < ln; q++) acc = __builtin_fmaf(pw[st + q], wt[q], acc);
         const float db = !(acc <= 1e-10f) ? 10.0f * log10f(acc) : -100.0f;   // (a NaN power stays NaN, as torch.clamp leaves it)
-        if constexpr (RG) flagged |= !(__builtin_fabsf(db) < __builtin_inff());
+        if constexpr (Clips::has_flags) flagged |= !(__builtin_fabsf(db) < __builtin_inff());
         if (p.frame_major) p.out[g * p.n_mels + m] = db;
-        else p.out[f.mel_base + (long)m * f.T + f.t] = db;
+        else p.out[f.base * p.n_mels + (long)m * f.T + f.t] = db;
     }
-    if constexpr (RG)
-        if (flagged) p.clip_bad[f.clip] = 1;   // (every writer stores the same value)
+    if constexpr (Clips::has_flags)
+        if (flagged) p.clips.flags[f.clip] = 1;   // (every writer stores the same value)
     __builtin_amdgcn_wave_barrier();   // the next frame overwrites the buffers
 }
 
-template <int LOG2M, bool RG = false>
-__global__ void __launch_bounds__(WG) logmel_any_kernel(AnyParams p) {
+template <int LOG2M, typename Clips>
+__global__ void __launch_bounds__(WG) logmel_any_kernel(AnyParams<Clips> p) {
     constexpr int M = 1 << LOG2M, N = 2 * M;
     extern __shared__ __attribute__((aligned(16))) float sm[];   // W_M (2M) | W_N (2M) | window (N) | per wave: z (N) + power (M + 4)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -209,11 +174,11 @@ __global__ void __launch_bounds__(WG) logmel_any_kernel(AnyParams p) {
     float* z = sm + 6 * M + (size_t)wave * (N + M + 4);
     float* pw = z + N;
     for (long g = (long)blockIdx.x * (WG / 64) + wave; g < p.n_frames; g += (long)gridDim.x * (WG / 64)) {
-        const FrameOf f = frame_of<RG>(p, g);
+        const ClipAt f = p.clips.by_frame(g);
         const FrameSrc load(p, f, win);
         fft_passes<M, 1, true>(lane, z, tw, load);
         untangle_frame(lane, M, z, twn, pw);
-        mel_db_store<RG>(lane, p, pw, g, f);
+        mel_db_store(lane, p, pw, g, f);
     }
 }
 
@@ -224,8 +189,9 @@ __global__ void __launch_bounds__(WG) logmel_any_kernel(AnyParams p) {
 // more than one butterfly; a wavefront's LDS instructions execute in order and the wave barriers keep the compiler
 // from moving an access across a pass boundary.  The window stays in global memory (read once per sample, coalesced):
 // two P-point buffers per wave are what the LDS is spent on.  blockDim.x / 64 waves per workgroup (1 .. 4, by LDS).
+template <typename Clips>
 struct MixedParams {
-    AnyParams a;
+    AnyParams<Clips> a;
     int P, npass;
     unsigned long long packed;   // lmx::Plan::packed
     const float* twp;            // P x (cos, -sin) of 2*pi*q/P
@@ -233,8 +199,9 @@ struct MixedParams {
     const float* bhat;           // form 2: P x transform of the chirp filter, / P
 };
 
-template <bool BLUE, bool RG>
-__device__ __forceinline__ void mixed_body(const MixedParams& p) {
+// (__launch_bounds__(WG) is the upper bound: the launch uses 64 .. 256 threads, launch_mixed)
+template <bool BLUE, typename Clips>
+__global__ void __launch_bounds__(WG) logmel_mixed_kernel(MixedParams<Clips> p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];   // W_P (2P) | W_N (2M) | per wave: two buffers of 2P
     const int M = p.a.n_fft / 2, P = p.P;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -245,31 +212,20 @@ __device__ __forceinline__ void mixed_body(const MixedParams& p) {
     __syncthreads();
     float* buf = sm + 2 * P + 2 * M + (size_t)wave * 4 * P;
     for (long g = (long)blockIdx.x * nw + wave; g < p.a.n_frames; g += (long)gridDim.x * nw) {
-        const FrameOf f = frame_of<RG>(p.a, g);
+        const ClipAt f = p.a.clips.by_frame(g);
         const FrameSrc src(p.a, f, p.a.win);
         float* cur = buf;           // after a transform: its result; the first pass of a transform writes `oth`
         float* oth = buf + 2 * P;
         const Lanes me{lane, lane + 1};
         frame_transform<BLUE>(me, M, P, p.npass, p.packed, tw, p.chirp, p.bhat, src, cur, oth, WaveBarrier{});
         untangle_lanes(me, M, cur, twn, oth, WaveBarrier{});
-        mel_db_store<RG>(lane, p.a, oth, g, f);
+        mel_db_store(lane, p.a, oth, g, f);
     }
 }
 
-// (__launch_bounds__(WG) is the upper bound: the launch uses 64 .. 256 threads, launch_mixed)
-template <bool BLUE>
-__global__ void __launch_bounds__(WG) logmel_mixed_kernel(MixedParams p) {
-    mixed_body<BLUE, false>(p);
-}
-// the ragged form of the two
-template <bool BLUE>
-__global__ void __launch_bounds__(WG) logmel_ragged_mx_kernel(MixedParams p) {
-    mixed_body<BLUE, true>(p);
-}
-
-template <int LOG2M>
-int launch_any(at_ctx* ctx, const AnyParams& p, hipStream_t stream) {
-    auto kernel = p.plan ? logmel_any_kernel<LOG2M, true> : logmel_any_kernel<LOG2M, false>;
+template <int LOG2M, typename Clips>
+int launch_any(at_ctx* ctx, const AnyParams<Clips>& p, hipStream_t stream) {
+    auto kernel = logmel_any_kernel<LOG2M, Clips>;
     constexpr int M = 1 << LOG2M, N = 2 * M;
     const size_t lds = ((size_t)6 * M + (size_t)(WG / 64) * (N + M + 4)) * sizeof(float);
     {
@@ -287,8 +243,8 @@ int launch_any(at_ctx* ctx, const AnyParams& p, hipStream_t stream) {
     return AT_OK;
 }
 
-template <bool BLUE>
-int launch_mixed(at_ctx* ctx, const MixedParams& p, hipStream_t stream) {
+template <bool BLUE, typename Clips>
+int launch_mixed(at_ctx* ctx, const MixedParams<Clips>& p, hipStream_t stream) {
     const size_t M = p.a.n_fft / 2, P = p.P;
     // as many waves per workgroup (at most four) as leave it inside a CU's 160 KiB of LDS
     const size_t tabs = (2 * P + 2 * M) * sizeof(float), per_wave = 4 * P * sizeof(float);
@@ -296,7 +252,7 @@ int launch_mixed(at_ctx* ctx, const MixedParams& p, hipStream_t stream) {
     while (nw > 1 && tabs + nw * per_wave > 160 * 1024) nw--;
     const size_t lds = tabs + nw * per_wave;
     if (lds > 160 * 1024) return at_fail(AT_E_INVALID, "at_logmel_f32: n_fft=%d needs %zu bytes of LDS", p.a.n_fft, lds);
-    auto kernel = p.a.plan ? logmel_ragged_mx_kernel<BLUE> : logmel_mixed_kernel<BLUE>;
+    auto kernel = logmel_mixed_kernel<BLUE, Clips>;
     {
         const int rc = at_raise_lds(ctx, reinterpret_cast<const void*>(kernel), lds);
         if (rc) return rc;
@@ -314,9 +270,9 @@ int launch_mixed(at_ctx* ctx, const MixedParams& p, hipStream_t stream) {
 
 // Tables for (sample_rate, n_fft, n_mels, filterbank values, form): window | W_M | W_N | form 2: W_P, chirp, filter
 // transform | start, len, off | band weights.  Form 0 = a power of two (logmel_any_kernel), else lmx::Plan::form.
-int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, int64_t wave_stride, int sample_rate,
-                  int n_fft, int hop, int n_mels, const float* fb_user_dev, float* out, int frame_major,
-                  const at_frontend_clip* plan_or_null, int32_t* clip_bad, int64_t ragged_frames, hipStream_t stream) {
+template <typename Clips>
+int at_logmel_any(at_ctx* ctx, const Clips& clips, int64_t n_frames, int sample_rate, int n_fft, int hop, int n_mels,
+                  const float* fb_user_dev, float* out, int frame_major, hipStream_t stream) {
     const int N = n_fft, M = N / 2, NBIN = M + 1;
     int log2m = 0;
     while ((1 << log2m) < M) log2m++;
@@ -343,20 +299,17 @@ int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, in
     int rc = at_logmel_resident(ctx, WS_LOGMEL_ANY, &ctx->lm_any, key, (lay.wts + (size_t)NBIN * n_mels) * 4, fb_user_dev,
                                 stream, build, &f);
     if (rc) return rc;
-    AnyParams p;
-    p.wave = wave; p.n_clips = n_clips; p.L = L; p.wave_stride = wave_stride;
+    AnyParams<Clips> p;
+    p.clips = clips;
     p.n_fft = N; p.log2m = log2m; p.hop = hop; p.n_mels = n_mels;
-    const int64_t T = plan_or_null ? 0 : at_num_frames(L, hop);
-    p.T = (int)T;
-    p.n_frames = plan_or_null ? ragged_frames : n_clips * T;
-    p.plan = plan_or_null; p.clip_bad = clip_bad;
+    p.n_frames = n_frames;
     p.win = f; p.twm = f + N; p.twn = f + N + 2 * M;
     p.fb_start = reinterpret_cast<const int*>(f + lay.ints);
     p.fb_len = p.fb_start + n_mels; p.fb_off = p.fb_start + 2 * n_mels;
     p.fb_wts = f + lay.wts;
     p.out = out; p.frame_major = frame_major;
     if (form != 0) {
-        MixedParams mp;
+        MixedParams<Clips> mp;
         mp.a = p;
         mp.P = P; mp.npass = plan.npass; mp.packed = plan.packed;
         mp.twp = form == FORM_BLUESTEIN ? f + head0 : p.twm;
@@ -375,3 +328,5 @@ int at_logmel_any(at_ctx* ctx, const float* wave, int64_t n_clips, int64_t L, in
     }
     return at_fail(AT_E_INVALID, "at_logmel_f32: n_fft=%d not supported", n_fft);
 }
+template int at_logmel_any(at_ctx*, const lmc::UniformClips&, int64_t, int, int, int, int, const float*, float*, int, hipStream_t);
+template int at_logmel_any(at_ctx*, const lmc::PlanClips&, int64_t, int, int, int, int, const float*, float*, int, hipStream_t);

@@ -163,28 +163,10 @@ class SpectrogramGenerator:
         found = [(i, self.find_audio_file(ytid)) for i, ytid in enumerate(source_files)]
         if self.ragged:
             return self._populate_specs_ragged(found)
-        # the batch's .flac files in one device decode; the waveforms stay on the device
-        be = self.spec_transformer.backend
-        flacs = [p for _, p in found if p and p.suffix.lower() == ".flac"]
-        decoded = dict(zip(flacs, zip(load_flac_batch(flacs, backend=be), be.flac_status))) if flacs else {}
-        waves, names = [], []
-        for i, audio_file_path in found:
-            if not audio_file_path:
-                continue
-            if audio_file_path in decoded:
-                got, status = decoded[audio_file_path]
-                if got is None and status == _FLAC_UNSUPPORTED and _torchaudio is not None:
-                    got = _torchaudio.load(audio_file_path)   # (Ogg-FLAC, 32-bit samples: as _load_audio does)
-                if got is None:
-                    self.logger.info(f"skipping {audio_file_path}: Failed to decode audio.")
-                    continue
-                waveform = self.resample(self.convert_to_mono(got[0]), got[1])
-            else:
-                waveform = self.preprocess_waveform(audio_file_path)
-            if waveform is None:
-                continue
-            waves.append(waveform)
-            names.append((i, audio_file_path))
+        # the batch as it decodes (.flac on the device, where the waveforms stay), then mono and one resampler call per clip
+        got = decode_batch([p for _, p in found], self.spec_transformer.backend, self.logger, load=self.load_waveform)
+        waves = [self.resample(self.convert_to_mono(g[0]), g[1]) for g in got if g is not None]
+        names = [f for f, g in zip(found, got) if g is not None]
 
         # one launch per distinct clip length
         by_len = {}

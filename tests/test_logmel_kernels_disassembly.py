@@ -40,7 +40,8 @@ def logmel_kernels(tmp_path_factory):
 
 def test_new_kernels_are_in_the_library(logmel_kernels):
     mixed = [n for n in logmel_kernels if "logmel_mixed_kernel" in n]
-    assert len(mixed) == 2, mixed                     # form 1 (mixed radix) and form 2 (Bluestein)
+    # form 1 (mixed radix, BLUE = false) and form 2 (Bluestein), each over the uniform and the plan clip map
+    assert len(mixed) == 4 and sum("ILb0E" in n for n in mixed) == 2 and sum("ILb1E" in n for n in mixed) == 2, mixed
     assert any("logmel_any_kernel" in n for n in logmel_kernels) and any("logmel_kernel" in n for n in logmel_kernels)
 
 

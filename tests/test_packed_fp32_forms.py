@@ -17,8 +17,9 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 LIB = ROOT / "audio_tokens_amd" / "libaudio_tokens_amd.so"
 OBJDUMP = Path("/opt/rocm/lib/llvm/bin/llvm-objdump")
-PRODUCERS = ("logmel_kernel", "logmel_any_kernel", "resample_kernel", "resample_tiled_kernel", "l2norm_rows_kernel",
-             "minmax_scale_kernel", "minmax_apply_kernel", "minmax_init_kernel", "conv1d_mel_kernel", "pairwise_sumsq")
+PRODUCERS = ("logmel_kernel", "logmel_any_kernel", "logmel_mixed_kernel", "resample_kernel", "resample_tiled_kernel",
+             "l2norm_rows_kernel", "minmax_scale_kernel", "minmax_extremes_kernel", "minmax_scale_pieces_kernel",
+             "minmax_init_kernel", "conv1d_mel_kernel", "pairwise_sumsq")
 
 
 @pytest.fixture(scope="module")
@@ -47,7 +48,8 @@ def kernels(tmp_path_factory):
 
 def test_producers_hold_no_packed_fp32_instruction(kernels):
     found = {p: [n for n in kernels if p in n] for p in PRODUCERS}
-    for p in ("logmel_kernel", "logmel_any_kernel", "resample", "l2norm_rows_kernel", "conv1d_mel_kernel"):
+    for p in ("logmel_kernel", "logmel_any_kernel", "logmel_mixed_kernel", "minmax_extremes_kernel",
+              "minmax_scale_pieces_kernel", "minmax_init_kernel", "resample", "l2norm_rows_kernel", "conv1d_mel_kernel"):
         assert any(p in n for n in kernels), f"{p}: not in the library"
     for p, names in found.items():
         for n in names:
