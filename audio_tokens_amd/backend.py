@@ -1051,6 +1051,42 @@ class HipBackend(HostHelpers):
             raise ValueError("Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)" % k)
         return s
 
+    def _f32_rows(self, t) -> torch.Tensor:
+        """A 2-D float32 device view whose rows are contiguous (stride(1) == 1, stride(0) >= the width): strided row
+        views pass as they are, anything else (other dtypes, bool / integer labels, host arrays) is converted."""
+        if isinstance(t, np.ndarray):
+            t = torch.from_numpy(np.ascontiguousarray(t))
+        if t.dim() != 2:
+            raise ValueError(f"Expected 2D array, got {t.dim()}D array instead")
+        if t.device != self.device:
+            t = t.to(self.device, non_blocking=t.is_pinned() if t.device.type == "cpu" else True)
+        if t.dtype != torch.float32:
+            t = t.float()
+        if t.shape[0] > 0 and t.shape[1] > 0 and not (t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) >= t.shape[1])):
+            t = t.contiguous()
+        return t
+
+    def average_precision(self, scores, labels):
+        """Exact per-class average precision (at_average_precision_f32: sklearn's average_precision_score per column, in
+        fp64): scores, labels [n, c] (made float32 on the device; strided row views are passed by their row stride, not
+        copied) -> (ap float64 [c], NaN for the classes without positives; n_pos int64 [c]; map_pair float64 [2] = the sum
+        of ap over the classes with positives and their number), device tensors, no synchronisation.  self.ap_flags
+        (device int32 [1]) holds the call's flag word: bit 0 a non-finite score, bit 1 a label other than 0 / 1."""
+        s, y = self._f32_rows(scores), self._f32_rows(labels)
+        if s.shape != y.shape:
+            raise ValueError(f"Found input variables with inconsistent shapes: {tuple(y.shape)}, {tuple(s.shape)}")
+        n, c = s.shape
+        ap = self.empty((c,), torch.float64)
+        n_pos = self.empty((c,), torch.int64)
+        pair = self.empty((2,), torch.float64)
+        self.ap_flags = flags = self.empty((1,), torch.int32)
+        ld_s = s.stride(0) if n > 1 else c
+        ld_y = y.stride(0) if n > 1 else c
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_average_precision_f32(self.ctx.handle, _ptr(s), ld_s, _ptr(y), ld_y, n, c, _ptr(ap),
+                                                         _ptr(n_pos), _ptr(pair), _ptr(flags), self._stream()))
+        return ap, n_pos, pair
+
 
 _default: dict = {}
 

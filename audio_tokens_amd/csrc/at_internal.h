@@ -84,6 +84,8 @@ enum at_ws_slot {
     WS_RAGGED_TAPS1,
     WS_RAGGED_TAPS2,
     WS_RAGGED_TAPS3,
+    WS_AVG_PRECISION,  // at_average_precision_f32: the two key buffers of a class chunk, tile records, tile partial sums
+    WS_AVG_PRECISION_TMP,   // its rocprim temp storage
     WS_NSLOTS
 };
 
@@ -122,6 +124,7 @@ struct at_debug {
     int filter_stats;     // AT_FILTER_STATS     1 = the sweeps count accumulators / tiles for at_prune_stats, at_filter_stats
     int accum_buckets;    // AT_ACCUM_BUCKETS    0 = member lists by radix sort (the only form for k > 16 384)
     int logmel_fallback;  // AT_LOGMEL_FALLBACK  1 = Bluestein form of the log-mel transform for every n_fft that is not a power of two
+    int ap_ws_mb;         // AT_AP_WS_MB         MiB the two key buffers of a class chunk of at_average_precision_f32 may take (default 1024; -m = chunks of m classes)
     int filter_timing;    // AT_FILTER_TIMING    1 = exact calls bracket their stage-1 kernel with two timing events (bench.py; off in the product)
 };
 
@@ -193,6 +196,9 @@ struct at_ctx {
     hipEvent_t knn_ev;        // behind the last at_knn_f32 (WS_KNN_IMG / WS_KNN are per context)
     hipStream_t knn_stream;
     int knn_used;
+    hipEvent_t ap_ev;         // behind the last at_average_precision_f32 (WS_AVG_PRECISION / _TMP are per context)
+    hipStream_t ap_stream;
+    int ap_used;
 };
 
 // makes launches of `func` with `bytes` of dynamic LDS legal on the context's device (at most one runtime call per

@@ -22,3 +22,15 @@ static inline int at_sort_pairs(at_ctx* ctx, int tmp_slot, rocprim::double_buffe
     AT_HIP(rocprim::radix_sort_pairs<at_radix_config>(tmp, tmp_bytes, keys, vals, n, begin_bit, end_bit, stream));
     return AT_OK;
 }
+
+// The same for keys alone; the result is in keys.current().
+template <typename Key>
+static inline int at_sort_keys(at_ctx* ctx, int tmp_slot, rocprim::double_buffer<Key>& keys, size_t n, unsigned begin_bit,
+                               unsigned end_bit, hipStream_t stream) {
+    size_t tmp_bytes = 0;
+    AT_HIP(rocprim::radix_sort_keys<at_radix_config>(nullptr, tmp_bytes, keys, n, begin_bit, end_bit, stream));
+    void* tmp = at_ws(ctx, tmp_slot, tmp_bytes, stream);
+    if (!tmp) return AT_E_NOMEM;
+    AT_HIP(rocprim::radix_sort_keys<at_radix_config>(tmp, tmp_bytes, keys, n, begin_bit, end_bit, stream));
+    return AT_OK;
+}

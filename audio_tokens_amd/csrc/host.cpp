@@ -71,6 +71,7 @@ const DebugField kDebugFields[] = {
     {"visit_bits", "AT_VISIT_BITS", &at_debug::visit_bits, 8},
     {"filter_timing", "AT_FILTER_TIMING", &at_debug::filter_timing, 0},
     {"logmel_fallback", "AT_LOGMEL_FALLBACK", &at_debug::logmel_fallback, 0},
+    {"ap_ws_mb", "AT_AP_WS_MB", &at_debug::ap_ws_mb, 1024},
 };
 }  // namespace
 
@@ -185,6 +186,7 @@ void at_destroy(at_ctx* ctx) {
     if (ctx->sum_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sum_ev));
     if (ctx->sil_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sil_ev));
     if (ctx->knn_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->knn_ev));
+    if (ctx->ap_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->ap_ev));
     if (ctx->filter_host_misc) (void)AT_HIP_TOLERATE(hipHostFree(ctx->filter_host_misc));
     at_logmel_tables_clear(&ctx->lm_fb);
     at_logmel_tables_clear(&ctx->lm_any);

@@ -10,6 +10,8 @@
         (processors/spec_tokenizer.py:123-127, 77)
     sklearn.metrics.silhouette_score                      ->  silhouette_score, silhouette_samples
         (processors/cluster_creator.py:115-117)
+    sklearn.metrics.average_precision_score (per class)   ->  average_precision, mean_average_precision
+        (utils/metrics_calculator.py:8-33; the class itself: audio_tokens_amd.utils.MetricsCalculator)
     torchaudio.load (of a .flac file)                     ->  load_flac, load_flac_batch
         (processors/spectrogram_generator.py:99)
     get_spectrogram + get_sequence                        ->  AudioTokenizer
@@ -36,7 +38,8 @@ import torch
 from .backend import default_backend
 
 __all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "normalize_rows", "silhouette_samples",
-           "silhouette_score", "load_flac", "load_flac_batch", "AudioTokenizer"]
+           "silhouette_score", "average_precision", "mean_average_precision", "load_flac", "load_flac_batch",
+           "AudioTokenizer"]
 
 
 def _is_host(x) -> bool:
@@ -834,3 +837,37 @@ def silhouette_score(X, labels, *, sample_size=None, random_state=None, backend=
     total = be.empty((1,), torch.float64)
     s = be.silhouette_samples(X, labels, sum_out=total)
     return float(total.item()) / s.numel()
+
+
+def _average_precision_checked(labels, scores, be):
+    """be.average_precision and the one host read behind it: (ap, n_pos) device tensors, map_pair as two floats."""
+    ap, n_pos, pair = be.average_precision(scores, labels)
+    tail = torch.cat([pair, be.ap_flags.double()]).cpu()        # the only synchronisation
+    flags = int(tail[2])
+    if flags & 1:
+        raise ValueError("Input y_score contains NaN or infinity.")
+    if flags & 2:
+        raise ValueError("Labels must be 0 or 1 in every class (multilabel-indicator format): found another value.")
+    return ap, n_pos, float(tail[0]), float(tail[1])
+
+
+def average_precision(labels, scores, backend=None):
+    """sklearn.metrics.average_precision_score(labels[:, j], scores[:, j]) for every class j on the device: numpy
+    float64 [c], NaN for the classes without a positive (the classes the reference skips).
+
+    labels, scores: [n, c] numpy arrays or torch tensors, on the host or the device; scores of other float dtypes and
+    bool / integer labels become float32 on the device.  Raises ValueError for NaN / infinite scores, as sklearn, and
+    for labels other than 0 and 1.  The recipe and its error bound are at_average_precision_f32's
+    (include/audio_tokens_amd.h)."""
+    be = backend or default_backend()
+    ap, _, _, _ = _average_precision_checked(labels, scores, be)
+    return be.to_host(ap)
+
+
+def mean_average_precision(labels, scores, backend=None):
+    """The reference's MetricsCalculator.calculate_mAP(labels, predictions): the mean of the per-class average precision
+    over the classes with at least one positive, 0.0 when there is none; a Python float.  Inputs and errors as for
+    average_precision; one host read (flags and the sum) at the end is the only synchronisation."""
+    be = backend or default_backend()
+    _, _, total, count = _average_precision_checked(labels, scores, be)
+    return total / count if count > 0 else 0.0

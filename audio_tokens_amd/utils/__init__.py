@@ -1,0 +1,3 @@
+from .metrics_calculator import MetricsCalculator
+
+__all__ = ["MetricsCalculator"]

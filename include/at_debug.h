@@ -8,12 +8,15 @@
  *                                 from the environment again; names:
  *                                   assign_variant filter_fused filter_sync prune_kernel prune_nb filter_screen
  *                                   filter_nb filter_wps2 dmin_kernel resample_simple accum_buckets filter_stats visit_bits
- *                                   filter_timing logmel_fallback strict_errors
+ *                                   filter_timing logmel_fallback ap_ws_mb strict_errors
  *                                 (logmel_fallback = 1 is the one switch that does NOT keep the bits: the even n_fft that
  *                                 are not powers of two all take the Bluestein form of the transform, so that it can be
  *                                 held against the mixed-radix form at the sizes that have both; same tolerance)
  *                                 (filter_stats = 1 makes the fp16-split sweeps count for the two calls below: one record
  *                                 per workgroup and a small reduction kernel behind every sweep; off by default)
+ *                                 (ap_ws_mb: the MiB the two key buffers of a class chunk of at_average_precision_f32
+ *                                 may take, default 1024; a negative value -m asks for chunks of exactly m classes; any
+ *                                 value gives the same bits, in more or fewer chunks)
  *                                 filter_timing = 1 brackets the stage-1 kernel of every exact call with two timing events
  *                                 (what at_filter_stats' sweep_ms sums; bench.py turns it on, the product leaves it off);
  *                                 strict_errors (process-wide, also AT_STRICT_ERRORS): a HIP error found pending in the

@@ -432,6 +432,27 @@ int at_token_stats_f64(at_ctx* ctx, const int64_t* counts, int k, int64_t* sorte
 int at_silhouette_f32(at_ctx* ctx, const float* x, int d, const int64_t* labels, int64_t n, float* s,
                       double* sum, int64_t* n_labels, void* stream);
 
+/* Exact per-class average precision and its mean over the classes with a positive: what
+ * MetricsCalculator.compute_metrics reports as mAP after every epoch (utils/metrics_calculator.py:8-33, called from
+ * processors/model_trainer.py:96: sklearn.metrics.average_precision_score per class, np.mean over the classes whose
+ * labels sum to more than 0).  scores, labels: DEVICE fp32, sample-major [n][c] with row strides ld_scores,
+ * ld_labels >= c (in floats); labels are 0.0 or 1.0.  Per class, sklearn's recipe: sort by score descending, equal
+ * scores (-0.0 == +0.0) form one group, and over the groups g in that order
+ *   ap[j] = sum_g fl(fl((tp_g - tp_{g-1}) / P) * fl(tp_g / cnt_g))      fp64; tp_g, cnt_g, P exact integers
+ * (tp_g / cnt_g: positives / samples up to the end of g; P = n_pos[j]); groups without a positive add nothing, the
+ * others are added in one fixed order, so |ap[j] - AP| <= 2 (P + 2) 2^-53.  NaN where n_pos[j] == 0.
+ *   ap: DEVICE double [c]; n_pos: DEVICE int64 [c];
+ *   map: DEVICE double [2]: the rounded sum of ap over the classes with positives (ascending class order) and their
+ *     number -- mAP = map[0] / map[1], or the reference's 0.0 when map[1] == 0;
+ *   flags: DEVICE int32: bit 0 = a score is NaN or infinite (sklearn raises ValueError), bit 1 = a label is neither 0.0
+ *     nor 1.0.  With a flag set the other outputs are meaningless.
+ * Deterministic, and the same bits for every chunking of the classes (the two sort buffers of a chunk stay within 1 GiB
+ * of context workspace unless a single class needs more); no host synchronisation once the workspace has its size.
+ * 1 <= n < 2^31 (and 16 n bytes of workspace for the keys of one class), c >= 1.  A call on another stream than the
+ * context's previous at_average_precision_f32 waits for that call. */
+int at_average_precision_f32(at_ctx* ctx, const float* scores, int64_t ld_scores, const float* labels, int64_t ld_labels,
+                             int64_t n, int c, double* ap, int64_t* n_pos, double* map, int32_t* flags, void* stream);
+
 /* The k nearest centroids under squared L2 (IndexFlatL2.search(x, k)).  dis(i,j) is at_assign_f32's value bit for bit
  * (the direct form for n < 20); a centroid is listed only if dis(i,j) < +inf (NaN never is).  Row i of the output holds
  * the k smallest (dis, j) in lexicographic order, ascending (ties: lower j first); slots with nothing to list hold
