@@ -1103,14 +1103,24 @@ __global__ void assign_small_kernel(const float* __restrict__ X, int n, int d,
     if (dist) dist[i] = best;
 }
 
+// the tiled centroid image of the dense and the hinted sweeps (tiles of 32 * na rows) in WS_CENT_IMG
+int prep_image(at_ctx* ctx, const float* c, int k, int d, int na, hipStream_t stream, float** img_out, int* ntiles_out) {
+    const int ntiles = (k + tile_rows(na) - 1) / tile_rows(na);
+    float* img = static_cast<float*>(at_ws(ctx, WS_CENT_IMG, sizeof(float) * (size_t)ntiles * tile_floats(d, na), stream));
+    if (!img) return AT_E_NOMEM;
+    AT_LAUNCH(prep_centroids_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, d, d, na, img);
+    *img_out = img;
+    *ntiles_out = ntiles;
+    return AT_OK;
+}
+
 template <int D, int NB, int NA, bool DMA, int WPS, bool SPEC = false>
 int launch_mfma(at_ctx* ctx, const float* x, int64_t n, const float* c, int k, int64_t* ids, float* dist,
                 hipStream_t stream) {
-    const int ntiles = (k + tile_rows(NA) - 1) / tile_rows(NA);
-    const size_t img_bytes = sizeof(float) * (size_t)ntiles * tile_floats(D, NA);
-    float* img = static_cast<float*>(at_ws(ctx, WS_CENT_IMG, img_bytes, stream));
-    if (!img) return AT_E_NOMEM;
-    AT_LAUNCH(prep_centroids_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, D, D, NA, img);
+    int ntiles = 0;
+    float* img = nullptr;
+    const int rc = prep_image(ctx, c, k, D, NA, stream, &img, &ntiles);
+    if (rc) return rc;
     const size_t lds = 2 * sizeof(float) * tile_floats(D, NA);
     const int64_t rows_per_wg = 4 * 32 * NB;
     const int64_t grid = (n + rows_per_wg - 1) / rows_per_wg;
@@ -1200,6 +1210,23 @@ extern "C" int at_assign_f32(at_ctx* ctx, const float* x, int64_t n, int d, cons
     return AT_OK;
 }
 
+// The hinted sweep of one shape (the two shipped: d = 64 and d = 128).
+template <int D, int NB, int NA>
+static int launch_hinted(at_ctx* ctx, const float* x, int64_t n, const float* c, int k, const int64_t* hint_ids,
+                         const uint32_t* order, const uint32_t* hint_sorted, int64_t* ids, float* dist, hipStream_t stream) {
+    int ntiles = 0;
+    float* img = nullptr;
+    const int rc = prep_image(ctx, c, k, D, NA, stream, &img, &ntiles);
+    if (rc) return rc;
+    const size_t lds = 2 * sizeof(float) * tile_floats(D, NA);
+    AT_RAISE_LDS(ctx, (assign_mfma_hinted_kernel<D, NB, NA>), lds);
+    const int64_t rows_per_wg = 4 * 32 * NB;
+    AT_LAUNCH((assign_mfma_hinted_kernel<D, NB, NA>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
+                       dim3(WG), lds, stream, x, (long)n, c, k, img, ntiles, order,
+                       reinterpret_cast<const long*>(hint_ids), hint_sorted, reinterpret_cast<long*>(ids), dist);
+    return AT_OK;
+}
+
 extern "C" int at_assign_hinted_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
                                     const int64_t* hint_ids, const uint32_t* order,
                                     const uint32_t* hint_sorted, int64_t* ids, float* dist, void* stream_) {
@@ -1213,365 +1240,48 @@ extern "C" int at_assign_hinted_f32(at_ctx* ctx, const float* x, int64_t n, int 
     AT_REQUIRE(x && c && ids, "at_assign_hinted_f32: null pointer");
     AT_REQUIRE(ids != hint_ids, "at_assign_hinted_f32: ids must not alias hint_ids");
     AT_HIP(hipSetDevice(ctx->device));
-    if (d == 64) {
-        constexpr int D = 64, NB = 2, NA = 4;
-        const int ntiles = (k + tile_rows(NA) - 1) / tile_rows(NA);
-        float* img = static_cast<float*>(at_ws(ctx, WS_CENT_IMG, sizeof(float) * (size_t)ntiles * tile_floats(D, NA), stream));
-        if (!img) return AT_E_NOMEM;
-        AT_LAUNCH(prep_centroids_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, D, D, NA, img);
-        const size_t lds = 2 * sizeof(float) * tile_floats(D, NA);
-        AT_RAISE_LDS(ctx, (assign_mfma_hinted_kernel<D, NB, NA>), lds);
-        const int64_t rows_per_wg = 4 * 32 * NB;
-        AT_LAUNCH((assign_mfma_hinted_kernel<D, NB, NA>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
-                           dim3(WG), lds, stream, x, (long)n, c, k, img, ntiles, order,
-                           reinterpret_cast<const long*>(hint_ids), hint_sorted, reinterpret_cast<long*>(ids), dist);
-        return AT_OK;
-    }
-    constexpr int D = 128, NB = 1, NA = 2;
-    const int ntiles = (k + tile_rows(NA) - 1) / tile_rows(NA);
-    float* img = static_cast<float*>(at_ws(ctx, WS_CENT_IMG, sizeof(float) * (size_t)ntiles * tile_floats(D, NA), stream));
-    if (!img) return AT_E_NOMEM;
-    AT_LAUNCH(prep_centroids_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, D, D, NA, img);
-    const size_t lds = 2 * sizeof(float) * tile_floats(D, NA);
-    AT_RAISE_LDS(ctx, (assign_mfma_hinted_kernel<D, NB, NA>), lds);
-    const int64_t rows_per_wg = 4 * 32 * NB;
-    AT_LAUNCH((assign_mfma_hinted_kernel<D, NB, NA>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
-                       dim3(WG), lds, stream, x, (long)n, c, k, img, ntiles, order,
-                       reinterpret_cast<const long*>(hint_ids), hint_sorted, reinterpret_cast<long*>(ids), dist);
-    return AT_OK;
+    if (d == 64) return launch_hinted<64, 2, 4>(ctx, x, n, c, k, hint_ids, order, hint_sorted, ids, dist, stream);
+    return launch_hinted<128, 1, 2>(ctx, x, n, c, k, hint_ids, order, hint_sorted, ids, dist, stream);
 }
 
-int at_prune_prepass(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
-                     const uint32_t* order, const uint32_t* hint_sorted, const float* dmin, int ng,
-                     float* bd_out, uint32_t* mask, int ngw, int mode, hipStream_t stream);
+// ---- the two launches of the exact pruned search that live here (driver: exact_search.cpp) --------------------
+// fp32 image (one tile per group, NA = 1: 32 rows, then |c|^2 at [0,32) and indices at [128,160)): every call claims
+// WS_CENT_IMG for it first, into call.img; it is built only where the fp32 sweep runs
+int at_pruned_image_claim(at_ctx* ctx, at_exact_call& call) {
+    call.img = static_cast<float*>(at_ws(ctx, WS_CENT_IMG, sizeof(float) * (size_t)call.ng * tile_floats(call.d, 1), call.stream));
+    return call.img ? AT_OK : AT_E_NOMEM;
+}
+
+int at_pruned_image_build(at_ctx* ctx, const at_exact_call& call) {
+    (void)ctx;
+    AT_LAUNCH(prep_centroids_perm_kernel, dim3(call.ng), dim3(WG), 0, call.stream, call.c, call.k, call.d, call.cperm,
+              call.ng * 32, 1, call.img);
+    return AT_OK;
+}
 
 template <int D, int NB>
-static int launch_pruned(at_ctx* ctx, const float* x, int64_t n, const float* c, int k, const uint32_t* order,
-                         const uint32_t* hint_sorted, const int32_t* cperm, int ng, const float* dmin, int mode,
-                         bool prepass_done, bool filter, int64_t* ids, float* dist, hipStream_t stream) {
-    const int kp = ng * 32;
-    const int ngw = (ng + 31) / 32;
-    const size_t img_bytes = sizeof(float) * (size_t)ng * tile_floats(D, 1);
-    // (the long-list redo below runs the pre-pass and the sweep over at least 64 rows, whatever n is)
-    const int64_t n_ws = n < 64 ? 64 : n;
-    const int64_t ntile32 = (n_ws + 31) / 32;
-    float* img = static_cast<float*>(at_ws(ctx, WS_CENT_IMG, img_bytes, stream));
-    float* bd = static_cast<float*>(at_ws(ctx, WS_PRUNE_BD, sizeof(float) * (size_t)n_ws, stream));
-    uint32_t* mask = static_cast<uint32_t*>(at_ws(ctx, WS_PRUNE_MASK, sizeof(uint32_t) * (size_t)ntile32 * ngw, stream));
-    if (!img || !bd || !mask) return AT_E_NOMEM;
-    // fp32 image (one tile per group, NA = 1: 32 rows, then |c|^2 at [0,32) and indices at [128,160)): built
-    // only where the fp32 sweep runs -- without the filter, or for its long-list redo
-    auto prep_fp32_image = [&]() -> int {
-        AT_LAUNCH(prep_centroids_perm_kernel, dim3(ng), dim3(WG), 0, stream, c, k, D, cperm, kp, 1, img);
-        return AT_OK;
-    };
-    if (!filter) {
-        int rc = prep_fp32_image();
-        if (rc) return rc;
-    }
-    // exact filtered calls without a pre-pass done by the caller: the sweep does it in its prologue
-    const bool fuse = filter && mode == 0 && !prepass_done && ctx->dbg.filter_fused != 0;   // (switch: 0 = separate pre-pass kernel)
-    if (!prepass_done && !fuse) {
-        int rc = at_prune_prepass(ctx, x, n, D, c, k, order, hint_sorted, dmin, ng, bd, mask, ngw, mode, stream);
-        if (rc) return rc;
-    }
+static int launch_pruned_sweep(at_ctx* ctx, const at_exact_call& call, int64_t n, const uint32_t* order,
+                               const uint32_t* hint_sorted) {
     const size_t lds = 2 * sizeof(float) * tile_floats(D, 1);
     const int64_t rows_per_wg = 32 * NB;
-    const uint32_t* order2 = order;
-    const uint32_t* hint2 = hint_sorted;
-    int64_t n2 = n;
-    if (filter) {
-        // Stage 1: fp16-split filter (filter.hip) names the winner of every row whose runner-up is
-        // provably out of reach and lists the others; stage 2 below redoes the listed rows with the
-        // fp32 sweep.  Coarse mode (guesses only) needs neither the list nor stage 2.
-        // statistics (and the list-length verdicts) of earlier calls whose words have arrived: polled, not waited for
-        int rcp = at_filter_resolve_pending(ctx, false);
-        if (rcp) return rcp;
-        const bool async_form = mode == 0 && !ctx->filter_force_sync && ctx->dbg.filter_sync != 1;
-        int slot = AT_FILTER_RING;
-        if (async_form) {
-            if (ctx->fring_count == AT_FILTER_RING) {   // the host is a whole ring ahead of the device: wait for the oldest
-                AT_HIP(hipEventSynchronize(ctx->fring[ctx->fring_head].copied));
-                rcp = at_filter_resolve_pending(ctx, false);
-                if (rcp) return rcp;
-            }
-            slot = (ctx->fring_head + ctx->fring_count) % AT_FILTER_RING;
-        } else if (mode == 0) {
-            rcp = at_filter_resolve_pending(ctx, true);   // the synchronous form reads its words at once: keep the order
-            if (rcp) return rcp;
-        }
-        rcp = at_filter_use_slot(ctx, slot);
-        if (rcp) return rcp;
-        unsigned* misc = static_cast<unsigned*>(at_ws(ctx, WS_FILTER_MISC, 1024, stream));
-        const size_t lstride = at_amb_stride(n);   // five arrays of 64 sub-lists: list | sorted | order | hints | aux
-        const unsigned amb_cap = at_amb_cap(n);
-        uint32_t* list = static_cast<uint32_t*>(at_ws(ctx, WS_FILTER_LIST, sizeof(uint32_t) * 5 * lstride, stream));
-        if (!misc || !list) return AT_E_NOMEM;
-        uint32_t* aux = list + 4 * lstride;
-        int rc = at_filter_sweep(ctx, x, n, D, c, k, order, cperm, ng, bd, mask, ngw, mode == 0 ? 1 : 0, ids, misc, list,
-                                 aux, nullptr, fuse ? hint_sorted : nullptr, fuse ? dmin : nullptr, fuse ? bd : nullptr,
-                                 (fuse || mode != 0) ? dist : nullptr, amb_cap, stream);
-        if (rc) return rc;
-        // (asynchronous fused calls: the distance pass rides in the launch that redoes the listed rows, below)
-        const bool finish_fused = dist && fuse && async_form;
-        if (dist && fuse && !finish_fused) {  // the sweep wrote the guess distances; the rows that moved get theirs here
-            rc = at_exact_dist_todo(ctx, x, n, D, c, k, ids, dist, stream);
-            if (rc) return rc;
-        } else if (dist && mode == 0 && !fuse) {
-            rc = at_exact_dist_rows(ctx, x, n, D, c, k, ids, dist, order, hint_sorted, bd, stream);
-            if (rc) return rc;
-        }  // (guess generators wrote an approximate distance themselves: it only orders the next visit)
-        if (mode != 0) return AT_OK;
-        // The list of rows to redo is normally short.  Asynchronous form: the redo kernel reads the list
-        // length on the device, the statistics words go to pinned memory and are folded in at the next
-        // call or query -- no host round trip here.  A call that turns out to have listed more than
-        // n/16 rows (badly scaled data) was still answered correctly (the redo strides over any length),
-        // but switches this context to the synchronous form below, whose redo of long lists is the
-        // fp32 MFMA sweep.
-        if (async_form) {
-            at_filter_slot& fs = ctx->fring[slot];
-            int64_t wgs = n / 64;                      // enough workgroups for a list of 1.5 % of the rows in one go
-            if (wgs < 256) wgs = 256;
-            if (wgs > 65535) wgs = 65535;
-            if (finish_fused)
-                rc = at_filter_finish(ctx, x, n, D, c, k, list, wgs, order, cperm, dmin, ng, misc, aux, ids, dist, misc + 64, amb_cap,
-                                      stream);
-            else
-                rc = at_filter_redo_rows(ctx, x, D, c, k, list, wgs, order, cperm, dmin, ng, misc, aux, ids, dist, misc + 64, amb_cap,
-                                         stream);
-            if (rc) return rc;
-            AT_HIP(hipMemcpyAsync(fs.host_misc, misc, 128 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-            AT_HIP(hipEventRecord(fs.copied, stream));
-            fs.rows = n;
-            ctx->fring_count++;
-            return AT_OK;
-        }
-        unsigned host_misc[128];
-        AT_HIP(hipMemcpyAsync(host_misc, misc, sizeof host_misc, hipMemcpyDeviceToHost, stream));
-        AT_HIP(hipStreamSynchronize(stream));
-        unsigned listed = 0;
-        for (unsigned s2 = 0; s2 < AT_AMB_SUBLISTS; s2++) listed += host_misc[64 + s2];
-        ctx->filter_rows += n;
-        ctx->filter_listed += listed;
-        ctx->filter_tiles += host_misc[4];
-        ctx->filter_refined += host_misc[5];
-        {
-            at_filter_slot& spare = ctx->fring[AT_FILTER_RING];
-            float ms = 0.0f;
-            if (spare.timed && AT_HIP_TOLERATE(hipEventElapsedTime(&ms, spare.ev[0], spare.ev[1])) == hipSuccess) {
-                ctx->filter_ms += ms;
-                ctx->filter_launches++;
-            }
-            spare.timed = 0;
-        }
-        if ((int64_t)listed * 16 <= n) ctx->filter_force_sync = 0;   // the data behave again
-        if (listed == 0) return AT_OK;
-        // short lists: one workgroup per row on the vector ALU (it walks the sub-lists itself); long ones (badly
-        // conditioned data, centroids outside the fp16 range): the fp32 MFMA sweep over the listed rows, which wants
-        // them in one piece
-        if ((int64_t)listed * 16 <= n) {
-            int64_t wgs = listed < 65535u ? (int64_t)listed : 65535;
-            return at_filter_redo_rows(ctx, x, D, c, k, list, wgs, order, cperm, dmin, ng, misc, aux, ids, dist, misc + 64, amb_cap,
-                                       stream);
-        }
-        rc = prep_fp32_image();
-        if (rc) return rc;
-        n2 = listed < 64 ? 64 : (int64_t)listed;
-        uint32_t* sorted = list + lstride;
-        uint32_t* order_amb = sorted + lstride;
-        uint32_t* hint_amb = order_amb + lstride;
-        // (listed <= n < the stride: the contiguous copy fits the `sorted` / `order` arrays; it then moves to the front of `list`)
-        rc = at_amb_compact(ctx, misc, amb_cap, list, aux, sorted, order_amb, stream);
-        if (rc) return rc;
-        AT_HIP(hipMemcpyAsync(list, sorted, sizeof(uint32_t) * listed, hipMemcpyDeviceToDevice, stream));
-        rc = at_filter_gather_ambiguous(ctx, list, sorted, listed, n2, order, ids, order_amb, hint_amb, stream);
-        if (rc) return rc;
-        order2 = order_amb;
-        hint2 = hint_amb;
-        rc = at_prune_prepass(ctx, x, n2, D, c, k, order2, hint2, dmin, ng, bd, mask, ngw, 0, stream);
-        if (rc) return rc;
-    }
     // d = 64: register-staged A operand (no LDS); AT_PRUNE_KERNEL=0 selects the LDS-DMA form (A/B aid)
     if (ctx->dbg.prune_kernel != 0 && D == 64 && NB <= 2)
-        AT_LAUNCH((assign_mfma_pruned_reg_kernel<D, NB>), dim3((unsigned)((n2 + rows_per_wg - 1) / rows_per_wg)),
-                           dim3(64), 0, stream, x, (long)n2, img, ng, order2, hint2, bd, mask, ngw,
-                           reinterpret_cast<long*>(ids), dist);
+        AT_LAUNCH((assign_mfma_pruned_reg_kernel<D, NB>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
+                           dim3(64), 0, call.stream, call.x, (long)n, call.img, call.ng, order, hint_sorted, call.bd, call.mask,
+                           call.ngw, reinterpret_cast<long*>(call.ids), call.dist);
     else
-        AT_LAUNCH((assign_mfma_pruned_kernel<D, NB>), dim3((unsigned)((n2 + rows_per_wg - 1) / rows_per_wg)),
-                           dim3(64), lds, stream, x, (long)n2, img, ng, order2, hint2, bd, mask, ngw,
-                           reinterpret_cast<long*>(ids), dist);
+        AT_LAUNCH((assign_mfma_pruned_kernel<D, NB>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
+                           dim3(64), lds, call.stream, call.x, (long)n, call.img, call.ng, order, hint_sorted, call.bd, call.mask,
+                           call.ngw, reinterpret_cast<long*>(call.ids), call.dist);
     return AT_OK;
 }
 
-extern "C" int at_assign_pruned_f32(at_ctx* ctx, const at_pruned_args* a, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    AT_REQUIRE(ctx && a, "at_assign_pruned_f32: ctx / args is null");
-    const float *x = a->x, *c = a->c, *dmin = a->bounds;
-    const int64_t n = a->n;
-    const int d = a->d, k = a->k, ng = a->ng;
-    const uint32_t *order = a->order, *hint_sorted = a->hint_sorted;
-    const int32_t* cperm = a->cperm;
-    int64_t* ids = a->ids;
-    float* dist = a->dist_or_null;
-    const int mode = a->guess_only ? 1 : 0;
-    const bool filter = a->use_filter != 0;
-    const int prepass_done = a->prepass_done ? 1 : 0;
-    AT_REQUIRE(x && c && order && hint_sorted && cperm && (dmin || mode == 1) && ids, "at_assign_pruned_f32: null pointer");
-    AT_REQUIRE(d == 64 || d == 128, "at_assign_pruned_f32: d must be 64 or 128");
-    AT_REQUIRE(n >= 20 && n < (int64_t)UINT32_MAX && k > 0 && ng > 0 && ng <= 512 && ng * 32 >= k,
-               "at_assign_pruned_f32: bad sizes n=%lld k=%d ng=%d", (long long)n, k, ng);
-    AT_REQUIRE(at_aligned16(x) && at_aligned16(c), "at_assign_pruned_f32: x and c must be 16-byte aligned");
-    AT_HIP(hipSetDevice(ctx->device));
-    ctx->img16_trusted = a->image_current != 0;  // consumed (and cleared) by the filter sweep
-    if (d == 64) {
+int at_pruned_sweep_f32(at_ctx* ctx, const at_exact_call& call, int64_t n, const uint32_t* order, const uint32_t* hint_sorted) {
+    if (call.d == 64) {
         const int nbsw = ctx->dbg.prune_nb;
-        if (nbsw == 4) return launch_pruned<64, 4>(ctx, x, n, c, k, order, hint_sorted, cperm, ng, dmin, mode, prepass_done != 0, filter, ids, dist, stream);
-        if (nbsw == 1) return launch_pruned<64, 1>(ctx, x, n, c, k, order, hint_sorted, cperm, ng, dmin, mode, prepass_done != 0, filter, ids, dist, stream);
-        return launch_pruned<64, 2>(ctx, x, n, c, k, order, hint_sorted, cperm, ng, dmin, mode, prepass_done != 0, filter, ids, dist, stream);
+        if (nbsw == 4) return launch_pruned_sweep<64, 4>(ctx, call, n, order, hint_sorted);
+        if (nbsw == 1) return launch_pruned_sweep<64, 1>(ctx, call, n, order, hint_sorted);
+        return launch_pruned_sweep<64, 2>(ctx, call, n, order, hint_sorted);
     }
-    return launch_pruned<128, 2>(ctx, x, n, c, k, order, hint_sorted, cperm, ng, dmin, mode, prepass_done != 0, filter, ids, dist, stream);
-}
-
-// The pre-pass of at_assign_pruned_f32 on its own (per-row bound + per-tile group masks, kept in the
-// context's workspace): lets a caller time or overlap it separately, then call
-// at_assign_pruned_f32(..., prepass_done = 1) with the same arguments.
-extern "C" int at_prune_mask_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
-                                 const uint32_t* order, const uint32_t* hint_sorted, int ng, const float* dmin,
-                                 int mode, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    AT_REQUIRE(ctx && x && c && order && hint_sorted && (dmin || mode == 1), "at_prune_mask_f32: null pointer");
-    AT_REQUIRE((d == 64 || d == 128) && n >= 20 && n < (int64_t)UINT32_MAX && ng > 0 && ng <= 512 && ng * 32 >= k,
-               "at_prune_mask_f32: bad sizes");
-    AT_HIP(hipSetDevice(ctx->device));
-    const int ngw = (ng + 31) / 32;
-    const int64_t ntile32 = (n + 31) / 32;
-    float* bd = static_cast<float*>(at_ws(ctx, WS_PRUNE_BD, sizeof(float) * (size_t)n, stream));
-    uint32_t* mask = static_cast<uint32_t*>(at_ws(ctx, WS_PRUNE_MASK, sizeof(uint32_t) * (size_t)ntile32 * ngw, stream));
-    if (!bd || !mask) return AT_E_NOMEM;
-    return at_prune_prepass(ctx, x, n, d, c, k, order, hint_sorted, dmin, ng, bd, mask, ngw, mode, stream);
-}
-
-// The statistics ring of the asynchronous exact calls (at_internal.h: at_filter_slot).
-// Life of a slot: claimed by at_filter_use_slot (timed = 0) -> the sweep records ev[0], ev[1] around its kernel only
-// under the switch filter_timing and then sets timed = 1 -> the call queues the copy of its statistics words and
-// records `copied` -> pushed (fring_count++) -> at_filter_resolve_pending reads the words once `copied` has
-// completed and the two timing events only if timed is set.  hipEventElapsedTime on an event that was never
-// recorded returns hipErrorInvalidResourceHandle and leaves it pending in the thread (the error round 2's launch
-// check then blamed on the next kernel launch): it is not called on such events any more, and its result is
-// consumed where it is tolerated.
-int at_filter_use_slot(at_ctx* ctx, int slot) {
-    AT_REQUIRE(slot >= 0 && slot <= AT_FILTER_RING, "at_filter_use_slot: slot %d out of range", slot);
-    if (!ctx->filter_host_misc) {
-        AT_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->filter_host_misc), (size_t)(AT_FILTER_RING + 1) * 128 * sizeof(unsigned),
-                             hipHostMallocDefault));
-        for (int s = 0; s <= AT_FILTER_RING; s++) ctx->fring[s].host_misc = ctx->filter_host_misc + (size_t)s * 128;
-    }
-    at_filter_slot& fs = ctx->fring[slot];
-    if (!fs.copied) AT_HIP(hipEventCreateWithFlags(&fs.copied, hipEventDisableTiming));
-    fs.timed = 0;
-    ctx->filter_slot = slot;
-    return AT_OK;
-}
-
-int at_filter_resolve_pending(at_ctx* ctx, bool wait_all) {
-    while (ctx->fring_count > 0) {
-        at_filter_slot& fs = ctx->fring[ctx->fring_head];
-        if (wait_all) {
-            AT_HIP(hipEventSynchronize(fs.copied));
-        } else {
-            const hipError_t q = hipEventQuery(fs.copied);
-            if (q == hipErrorNotReady) break;   // an answer, not a failure (and the one code HIP does not keep pending)
-            AT_HIP(q);
-        }
-        const unsigned* hm = fs.host_misc;
-        unsigned listed = 0;
-        for (unsigned s2 = 0; s2 < AT_AMB_SUBLISTS; s2++) listed += hm[64 + s2];
-        ctx->filter_rows += fs.rows;
-        ctx->filter_listed += listed;
-        ctx->filter_tiles += hm[4];
-        ctx->filter_refined += hm[5];
-        if (fs.timed) {   // (both events were recorded before `copied`, on the same stream: they have completed)
-            float ms = 0.0f;
-            if (AT_HIP_TOLERATE(hipEventElapsedTime(&ms, fs.ev[0], fs.ev[1])) == hipSuccess) {
-                ctx->filter_ms += ms;
-                ctx->filter_launches++;
-            }
-            fs.timed = 0;
-        }
-        if ((int64_t)listed * 16 > fs.rows) ctx->filter_force_sync = 1;
-        ctx->fring_head = (ctx->fring_head + 1) % AT_FILTER_RING;
-        ctx->fring_count--;
-    }
-    return AT_OK;
-}
-
-extern "C" int at_filter_stats(at_ctx* ctx, int64_t* rows, int64_t* listed, double* sweep_ms, int64_t* sweeps,
-                               int64_t* tiles, int64_t* refined, int reset) {
-    AT_REQUIRE(ctx && rows && listed, "at_filter_stats: bad arguments");
-    {
-        int rcp = at_filter_resolve_pending(ctx, true);
-        if (rcp) return rcp;
-    }
-    *rows = ctx->filter_rows;
-    *listed = ctx->filter_listed;
-    if (sweep_ms) *sweep_ms = ctx->filter_ms;
-    if (sweeps) *sweeps = ctx->filter_launches;
-    if (tiles) *tiles = ctx->filter_tiles;
-    if (refined) *refined = ctx->filter_refined;
-    if (reset) {
-        ctx->filter_rows = ctx->filter_listed = ctx->filter_launches = ctx->filter_tiles = ctx->filter_refined = 0;
-        ctx->filter_ms = 0.0;
-    }
-    return AT_OK;
-}
-
-// Test hook: pre-pass + stage 1 only.  approx[2i] = approximate |c|^2 - 2 x.c of row i's winner,
-// approx[2i+1] = gap to the runner-up; ids = the winners; *listed = rows the filter would hand to the
-// fp32 sweep; tau_ab[0..1] = the coefficients of the acceptance threshold tau = a (|x|^2 + max|c|^2) + b.
-extern "C" int at_filter_probe_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
-                                   const uint32_t* order, const uint32_t* hint_sorted, const int32_t* cperm, int ng,
-                                   const float* dmin, int64_t* ids, float* approx, int64_t* listed, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    AT_REQUIRE(ctx && x && c && order && hint_sorted && cperm && dmin && ids && approx && listed,
-               "at_filter_probe_f32: null pointer");
-    AT_REQUIRE((d == 64 || d == 128) && n >= 20 && n < (int64_t)UINT32_MAX && k > 0 && ng > 0 && ng <= 512 && ng * 32 >= k,
-               "at_filter_probe_f32: bad sizes");
-    AT_HIP(hipSetDevice(ctx->device));
-    const int ngw = (ng + 31) / 32;
-    const int64_t ntile32 = (n + 31) / 32;
-    float* bd = static_cast<float*>(at_ws(ctx, WS_PRUNE_BD, sizeof(float) * (size_t)n, stream));
-    uint32_t* mask = static_cast<uint32_t*>(at_ws(ctx, WS_PRUNE_MASK, sizeof(uint32_t) * (size_t)ntile32 * ngw, stream));
-    unsigned* misc = static_cast<unsigned*>(at_ws(ctx, WS_FILTER_MISC, 1024, stream));
-    const size_t lstride = at_amb_stride(n);
-    uint32_t* list = static_cast<uint32_t*>(at_ws(ctx, WS_FILTER_LIST, sizeof(uint32_t) * 5 * lstride, stream));
-    if (!bd || !mask || !misc || !list) return AT_E_NOMEM;
-    int rc = at_prune_prepass(ctx, x, n, d, c, k, order, hint_sorted, dmin, ng, bd, mask, ngw, 0, stream);
-    if (rc) return rc;
-    rc = at_filter_use_slot(ctx, AT_FILTER_RING);   // (a call outside the ring: the spare slot)
-    if (rc) return rc;
-    rc = at_filter_sweep(ctx, x, n, d, c, k, order, cperm, ng, bd, mask, ngw, 1, ids, misc, list,
-                         list + 4 * lstride, approx, nullptr, nullptr, nullptr, nullptr, at_amb_cap(n), stream);
-    if (rc) return rc;
-    unsigned cnts[AT_AMB_SUBLISTS];
-    AT_HIP(hipMemcpyAsync(cnts, misc + 64, sizeof cnts, hipMemcpyDeviceToHost, stream));
-    AT_HIP(hipStreamSynchronize(stream));
-    int64_t cnt = 0;
-    for (unsigned s2 = 0; s2 < AT_AMB_SUBLISTS; s2++) cnt += cnts[s2];
-    *listed = cnt;
-    return AT_OK;
-}
-
-// Guess generator without a pre-sort, for rows whose own order is coherent (the frames of a clip follow
-// one another): nearest of the ng group means -> the groups its neighbour table names -> best centroid
-// among them, in one launch.  ids are guesses (feed at_visit_order_f32 / at_assign_pruned_f32), dist (optional)
-// approximate distances.
-extern "C" int at_assign_coarse_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
-                                    const int32_t* cperm, int ng, const float* means, const uint32_t* gnbr,
-                                    int64_t* ids, float* dist, void* stream_) {
-    AT_REQUIRE(ctx && x && c && cperm && means && gnbr && ids, "at_assign_coarse_f32: null pointer");
-    AT_REQUIRE((d == 64 || d == 128) && n >= 1 && n < (int64_t)UINT32_MAX && k > 0 && ng > 0 && ng <= 512 && ng * 32 >= k,
-               "at_assign_coarse_f32: bad sizes");
-    AT_REQUIRE(at_aligned16(x) && at_aligned16(c) && at_aligned16(means), "at_assign_coarse_f32: pointers must be 16-byte aligned");
-    AT_HIP(hipSetDevice(ctx->device));
-    return at_filter_coarse(ctx, x, n, d, c, k, cperm, ng, means, gnbr, ids, dist, (hipStream_t)stream_);
+    return launch_pruned_sweep<128, 2>(ctx, call, n, order, hint_sorted);
 }

@@ -13,6 +13,7 @@
 
 #include "../../include/audio_tokens_amd.h"
 #include "../../include/at_debug.h"
+#include "exact_plan.h"
 
 // Kernels that a caller may put on a stream of its own beside the k-means / tokenise sweeps (the pipeline computes the
 // log-mel frames of later batches on the context's background stream) are compiled WITHOUT packed-fp32 vector
@@ -96,7 +97,7 @@ constexpr int AT_RS_COPY_PER_BLOCK = 4096;   // samples per workgroup where ther
 
 // Asynchronous exact calls leave their statistics words (and the events that time their stage-1 kernel) in a
 // ring of slots; slots are folded into the totals when their copy has arrived -- polled, never waited for, unless
-// the ring is full or a query asks for the totals.
+// the ring is full or a query asks for the totals (exact_search.cpp).
 constexpr int AT_FILTER_RING = 64;
 struct at_filter_slot {
     unsigned* host_misc;   // pinned, 128 words
@@ -104,6 +105,17 @@ struct at_filter_slot {
     hipEvent_t ev[2];      // around the stage-1 kernel (created on first use, and only under the switch filter_timing)
     int timed;             // both of ev[] were recorded by the call that holds this slot (else they are not read)
     int64_t rows;
+};
+// What a context keeps of the fp16-split filter between exact calls.
+struct at_filter_state {
+    exact_plan::Totals tot;      // rows swept / listed, tiles multiplied / refined; force_sync: a call whose list was long
+                                 // switches the context to the synchronous form (with its fp32 MFMA redo) from then on
+    double ms;                   // summed stage-1 kernel time, over `launches` launches
+    int64_t launches;
+    int slot;                    // the ring slot (or AT_FILTER_RING, the spare) the sweep being queued belongs to
+    unsigned* host_misc;         // pinned, (AT_FILTER_RING + 1) x 128 words
+    at_filter_slot ring[AT_FILTER_RING + 1];   // (the extra slot lends its timing events to the synchronous form)
+    int head, count;             // oldest pending slot, number of pending slots
 };
 
 // Development switches (include/at_debug.h).  Read from the environment ONCE, in at_create -- never on a call
@@ -155,19 +167,7 @@ struct at_ctx {
     int rs_orig, rs_new;  // what WS_RESAMPLE_TAPS currently holds
     int rg_taps[4][2];    // what WS_RAGGED_TAPS0 .. 3 hold (rate pairs; 0 = nothing), replaced round robin
     int rg_next;
-    int64_t filter_rows, filter_listed;  // fp16-split filter: rows swept / rows handed to the fp32 redo
-    int filter_slot;                     // the ring slot (or AT_FILTER_RING, the spare) the sweep being queued belongs to
-    double filter_ms;                    // summed stage-1 kernel time, over filter_launches launches
-    int64_t filter_launches;
-    int64_t filter_tiles, filter_refined;
-    // asynchronous exact calls: the statistics words of the last call are copied to pinned memory and folded
-    // into the totals at the next call / query; a call whose list was long switches the context to the
-    // synchronous form (with its fp32 MFMA redo) from then on
-    unsigned* filter_host_misc;          // pinned, (AT_FILTER_RING + 1) x 64 words
-    at_filter_slot fring[AT_FILTER_RING + 1];   // (the extra slot lends its timing events to the synchronous form)
-    int fring_head, fring_count;         // oldest pending slot, number of pending slots
-    int filter_force_sync;
-  // 32x32 tiles multiplied (hi*hi) / refined (lo products too), exact calls
+    at_filter_state filter;
     hipStream_t side_stream;             // centroid_accum: long member lists beside the short ones
     hipStream_t background_stream;       // at_background_stream: lowest priority, lent to the caller
     hipEvent_t side_ev[2];
@@ -298,36 +298,60 @@ static inline hipError_t at_launch_raw(void (*kern)(KArgs...), dim3 grid, dim3 b
         if (rc_) return rc_;                                                                   \
     } while (0)
 
-// filter.hip (fp16-split filter of the pruned sweep)
-int at_filter_sweep(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const uint32_t* order,
-                    const int32_t* cperm, int ng, const float* bd, const uint32_t* mask, int ngw, int collect,
-                    int64_t* ids, unsigned* misc, uint32_t* amb_list, uint32_t* amb_aux, float* approx_out,
-                    const uint32_t* fuse_hint_sorted, const float* fuse_dmin, float* fuse_bd_out, float* fuse_dist_out,
-                    unsigned amb_cap, hipStream_t stream);
-// the rows a sweep lists for the redo: 64 sub-lists of amb_cap slots each (counters at misc[64 ..]), arrays of
-// at_amb_stride(n) words
-constexpr unsigned AT_AMB_SUBLISTS = 64;
+// ---- the exact pruned search (at_assign_pruned_f32): driver in exact_search.cpp, launches in prune.hip, filter.hip, assign.hip
+// sub-lists of amb_cap slots each, arrays of at_amb_stride(n) words (AT_AMB_SUBLISTS: exact_plan.h)
 static inline unsigned at_amb_cap(int64_t n) { return (unsigned)(n / AT_AMB_SUBLISTS + 128); }
 static inline size_t at_amb_stride(int64_t n) { return (size_t)at_amb_cap(n) * AT_AMB_SUBLISTS; }
-int at_amb_compact(at_ctx* ctx, const unsigned* misc, unsigned amb_cap, const uint32_t* list, const uint32_t* aux,
-                   uint32_t* list_out, uint32_t* aux_out, hipStream_t stream);
-int at_exact_dist_todo(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const int64_t* ids,
-                       float* dist, hipStream_t stream);
-int at_exact_dist_rows(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const int64_t* ids,
-                       float* dist, const uint32_t* order, const uint32_t* hint_sorted, const float* bd,
-                       hipStream_t stream);
-int at_filter_gather_ambiguous(at_ctx* ctx, uint32_t* amb_list, uint32_t* amb_sorted, int64_t m_valid, int64_t m,
-                               const uint32_t* order, const int64_t* ids, uint32_t* order_amb, uint32_t* hint_amb,
-                               hipStream_t stream);
 
-int at_filter_finish(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const uint32_t* list, int64_t redo_wgs,
-                     const uint32_t* order, const int32_t* cperm, const float* dmin, int ng, const unsigned* misc,
-                     const uint32_t* aux, int64_t* ids, float* dist, const unsigned* count_dev, unsigned amb_cap,
-                     hipStream_t stream);
-int at_filter_redo_rows(at_ctx* ctx, const float* x, int d, const float* c, int k, const uint32_t* list, int64_t m,
-                        const uint32_t* order, const int32_t* cperm, const float* dmin, int ng, const unsigned* misc,
-                        const uint32_t* aux, int64_t* ids, float* dist, const unsigned* count_dev, unsigned amb_cap,
-                        hipStream_t stream);
+// One exact call: the caller's arguments, the workspace claimed for it and its stream.  The launches below read what
+// they need from it; what varies between two launches of one call stays a parameter.
+struct at_exact_call {
+    const float* x;
+    int64_t n;
+    int d;
+    const float* c;
+    int k;
+    const uint32_t* order;
+    const uint32_t* hint_sorted;
+    const int32_t* cperm;
+    int ng;
+    const float* dmin;
+    int64_t* ids;
+    float* dist;
+    // claimed (exact_search.cpp): the fp32 image of the pruned sweep, the pre-pass outputs ...
+    float* img;
+    float* bd;          // exact distance to the guess, per visiting position
+    uint32_t* mask;     // per 32-row tile, one bit per 32-centroid group (ngw words)
+    int ngw;
+    // ... and, for filtered calls, the statistics words and the five arrays of lstride words each
+    unsigned* misc;     // 128 words: max|c|^2, statistics, sub-list lengths at [64 ..)
+    uint32_t *list, *sorted, *order_amb, *hint_amb, *aux;
+    unsigned amb_cap;
+    size_t lstride;
+    hipStream_t stream;
+};
+
+// prune.hip: per-row bound and per-tile group masks of the first n rows visited in `order` (the call's own, or the
+// gathered list of a long redo), into call.bd / call.mask
+int at_prune_prepass(at_ctx* ctx, const at_exact_call& call, int64_t n, const uint32_t* order, const uint32_t* hint_sorted,
+                     int mode);
+// assign.hip: WS_CENT_IMG claimed into call.img for the permuted fp32 image (one tile per group), the image built there,
+// and the fp32 pruned sweep over n rows (kernel by d and the switches prune_nb / prune_kernel)
+int at_pruned_image_claim(at_ctx* ctx, at_exact_call& call);
+int at_pruned_image_build(at_ctx* ctx, const at_exact_call& call);
+int at_pruned_sweep_f32(at_ctx* ctx, const at_exact_call& call, int64_t n, const uint32_t* order, const uint32_t* hint_sorted);
+// filter.hip: stage 1 (collect: list the rows it cannot settle; fused_prepass: it computes call.bd and its own masks;
+// dist_out: guess distances / a guess generator's approximate ones; approx_out: at_filter_probe_f32)
+int at_filter_sweep(at_ctx* ctx, const at_exact_call& call, int collect, bool fused_prepass, float* dist_out,
+                    float* approx_out);
+// ... the distance passes and the redo of the listed rows (m: list length, or the number of workgroups to launch)
+int at_exact_dist_todo(at_ctx* ctx, const at_exact_call& call);
+int at_exact_dist_rows(at_ctx* ctx, const at_exact_call& call);
+int at_filter_redo_rows(at_ctx* ctx, const at_exact_call& call, int64_t m);
+int at_filter_finish(at_ctx* ctx, const at_exact_call& call, int64_t redo_wgs);
+// ... and the long-list redo: sub-lists -> contiguous (sorted, order_amb), then sorted and expanded to m >= m_valid rows
+int at_amb_compact(at_ctx* ctx, const at_exact_call& call);
+int at_filter_gather_ambiguous(at_ctx* ctx, const at_exact_call& call, int64_t m_valid, int64_t m);
 
 // logmel.hip: the resident tables of a log-mel slot for `key` (sr, nfft, nmels, hop, form; the rest 0) and the caller's
 // filterbank (device [nfft/2 + 1][nmels], compared by value) or the library's own (null); *tabs = the slot's device pointer.
@@ -368,7 +392,7 @@ int at_group_min_dist_f16(at_ctx* ctx, const float* c, int k, int d, const int32
 int at_filter_coarse(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const int32_t* cperm, int ng,
                      const float* means, const uint32_t* gnbr, int64_t* ids, float* dist, hipStream_t stream);
 
-// wait_all: fold every pending slot (blocking); otherwise only those whose copy has already arrived
+// exact_search.cpp.  wait_all: fold every pending slot (blocking); otherwise only those whose copy has already arrived
 int at_filter_resolve_pending(at_ctx* ctx, bool wait_all);
 // the sweep queued next belongs to ring slot `slot` (AT_FILTER_RING: the spare, for calls outside the ring); creates
 // what the slot needs on first use and marks its timing events as not recorded

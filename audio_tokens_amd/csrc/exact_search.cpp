@@ -1,0 +1,303 @@
+// exact_search.cpp -- the host side of the exact pruned nearest-centroid search: at_assign_pruned_f32, its pre-pass and
+// probe entry points, the statistics ring of its asynchronous form and at_filter_stats.  No kernel lives here: the
+// launches are at_prune_prepass (prune.hip), at_filter_* / at_exact_dist_* / at_amb_compact (filter.hip) and
+// at_pruned_image_* / at_pruned_sweep_f32 (assign.hip); the decisions that need no device are in exact_plan.h.
+//
+// A filtered exact call finishes in one of four ways (tests/test_gpu_hard_data.py walks all of them):
+//   asynchronous form  the redo kernels read the list length on the device, whatever it is (finish_async); the call's
+//                      statistics words go to a ring slot and are folded into the totals at a later call or query.  A
+//                      call that turns out to have listed more than n/16 rows (badly scaled data) was still answered
+//                      correctly, but switches the context to the synchronous form;
+//   synchronous form   the words are read at once: nothing listed, a short list (at_filter_redo_rows), or a long one
+//                      (finish_sync_long: the fp32 MFMA sweep over the listed rows).  A short list switches back.
+#include "at_internal.h"
+
+namespace {
+
+// Sizes every entry point over grouped centroids shares (n_min: 20 where the fp32 sweep may run, 1 for the guess generator).
+bool grouped_sizes_ok(int64_t n, int64_t n_min, int d, int k, int ng) {
+    return (d == 64 || d == 128) && n >= n_min && n < (int64_t)UINT32_MAX && ng > 0 && ng <= 512 && ng * 32 >= k;
+}
+
+// ---- workspace -------------------------------------------------------------------------------------------------
+// The pre-pass outputs, for max(n, 64) rows: the long-list redo runs the pre-pass and the sweep over at least 64 rows,
+// whatever n is.  Nothing of the filter is touched.
+int claim_prepass(at_ctx* ctx, at_exact_call& call) {
+    const int64_t n_ws = call.n < 64 ? 64 : call.n;
+    call.ngw = (call.ng + 31) / 32;
+    call.bd = static_cast<float*>(at_ws(ctx, WS_PRUNE_BD, sizeof(float) * (size_t)n_ws, call.stream));
+    call.mask = static_cast<uint32_t*>(
+        at_ws(ctx, WS_PRUNE_MASK, sizeof(uint32_t) * (size_t)((n_ws + 31) / 32) * call.ngw, call.stream));
+    return call.bd && call.mask ? AT_OK : AT_E_NOMEM;
+}
+
+// The filter's statistics words and its five arrays of 64 sub-lists: list | sorted | order | hints | aux.
+int claim_filter(at_ctx* ctx, at_exact_call& call) {
+    call.lstride = at_amb_stride(call.n);
+    call.amb_cap = at_amb_cap(call.n);
+    call.misc = static_cast<unsigned*>(at_ws(ctx, WS_FILTER_MISC, 1024, call.stream));
+    call.list = static_cast<uint32_t*>(at_ws(ctx, WS_FILTER_LIST, sizeof(uint32_t) * 5 * call.lstride, call.stream));
+    if (!call.misc || !call.list) return AT_E_NOMEM;
+    call.sorted = call.list + call.lstride;
+    call.order_amb = call.sorted + call.lstride;
+    call.hint_amb = call.order_amb + call.lstride;
+    call.aux = call.hint_amb + call.lstride;
+    return AT_OK;
+}
+
+// ---- the statistics ring (at_internal.h: at_filter_slot) ---------------------------------------------------------
+// Life of a slot: claimed by at_filter_use_slot (timed = 0) -> the sweep records ev[0], ev[1] around its kernel only
+// under the switch filter_timing and then sets timed = 1 -> the call queues the copy of its statistics words and
+// records `copied` -> pushed (count++) -> at_filter_resolve_pending reads the words once `copied` has completed and the
+// two timing events only if timed is set.  hipEventElapsedTime on an event that was never recorded returns
+// hipErrorInvalidResourceHandle and leaves it pending in the thread: it is not called on such events, and its result
+// is consumed where it is tolerated.
+
+// The stage-1 kernel time of the call whose events `fs` lent (both were recorded before its words were read, on the
+// same stream: they have completed).
+void fold_timing(at_filter_state& f, at_filter_slot& fs) {
+    float ms = 0.0f;
+    if (fs.timed && AT_HIP_TOLERATE(hipEventElapsedTime(&ms, fs.ev[0], fs.ev[1])) == hipSuccess) {
+        f.ms += ms;
+        f.launches++;
+    }
+    fs.timed = 0;
+}
+
+// The slot of a call that is about to queue its filter sweep.  Asynchronous form: the next of the ring, waiting for the
+// oldest only when the host is a whole ring ahead of the device.  Synchronous form: the spare, with every pending slot
+// folded first (it reads its own words at once: keep the order).  Guess generators leave no words behind: the spare.
+int take_slot(at_ctx* ctx, const exact_plan::Plan& plan, int* slot) {
+    at_filter_state& f = ctx->filter;
+    *slot = AT_FILTER_RING;
+    if (plan.async_form) {
+        if (f.count == AT_FILTER_RING) {
+            AT_HIP(hipEventSynchronize(f.ring[f.head].copied));
+            const int rc = at_filter_resolve_pending(ctx, false);
+            if (rc) return rc;
+        }
+        *slot = (f.head + f.count) % AT_FILTER_RING;
+    } else if (plan.stage2) {
+        const int rc = at_filter_resolve_pending(ctx, true);
+        if (rc) return rc;
+    }
+    return at_filter_use_slot(ctx, *slot);
+}
+
+// ---- the three ways to finish a filtered exact call that listed rows -----------------------------------------------
+int finish_async(at_ctx* ctx, const at_exact_call& call, const exact_plan::Plan& plan, int slot) {
+    at_filter_slot& fs = ctx->filter.ring[slot];
+    const int64_t wgs = exact_plan::async_redo_wgs(call.n);
+    const int rc = plan.dist == exact_plan::DIST_FROM_FINISH ? at_filter_finish(ctx, call, wgs) : at_filter_redo_rows(ctx, call, wgs);
+    if (rc) return rc;
+    AT_HIP(hipMemcpyAsync(fs.host_misc, call.misc, 128 * sizeof(unsigned), hipMemcpyDeviceToHost, call.stream));
+    AT_HIP(hipEventRecord(fs.copied, call.stream));
+    fs.rows = call.n;
+    ctx->filter.count++;
+    return AT_OK;
+}
+
+// The listed rows in one piece (listed <= n < the stride: the contiguous copy fits the `sorted` / `order_amb` arrays; it
+// then moves to the front of `list`), sorted and padded to n2 rows, then a fresh pre-pass and the fp32 sweep over them.
+int finish_sync_long(at_ctx* ctx, const at_exact_call& call, int64_t listed, int64_t n2) {
+    int rc = at_pruned_image_build(ctx, call);
+    if (rc) return rc;
+    rc = at_amb_compact(ctx, call);
+    if (rc) return rc;
+    AT_HIP(hipMemcpyAsync(call.list, call.sorted, sizeof(uint32_t) * listed, hipMemcpyDeviceToDevice, call.stream));
+    rc = at_filter_gather_ambiguous(ctx, call, listed, n2);
+    if (rc) return rc;
+    rc = at_prune_prepass(ctx, call, n2, call.order_amb, call.hint_amb, 0);
+    if (rc) return rc;
+    return at_pruned_sweep_f32(ctx, call, n2, call.order_amb, call.hint_amb);
+}
+
+// The synchronous form: the call's words at once, then the finish they ask for.
+int finish_sync(at_ctx* ctx, const at_exact_call& call) {
+    unsigned host_misc[128];
+    AT_HIP(hipMemcpyAsync(host_misc, call.misc, sizeof host_misc, hipMemcpyDeviceToHost, call.stream));
+    AT_HIP(hipStreamSynchronize(call.stream));
+    const int64_t listed = exact_plan::fold_sync_call(ctx->filter.tot, host_misc, call.n);
+    fold_timing(ctx->filter, ctx->filter.ring[AT_FILTER_RING]);
+    const exact_plan::SyncRedo redo = exact_plan::sync_redo(listed, call.n);
+    if (redo.kind == exact_plan::REDO_SHORT) return at_filter_redo_rows(ctx, call, redo.count);
+    if (redo.kind == exact_plan::REDO_LONG) return finish_sync_long(ctx, call, listed, redo.count);
+    return AT_OK;
+}
+
+// The driver: plan, claim, pre-pass, sweep, distance pass, finish.
+int exact_search(at_ctx* ctx, at_exact_call& call, int mode, bool prepass_done, bool use_filter) {
+    if (use_filter) {   // verdicts of earlier calls whose words have arrived (polled, not waited for) count for this plan
+        const int rcp = at_filter_resolve_pending(ctx, false);
+        if (rcp) return rcp;
+    }
+    const exact_plan::Plan plan = exact_plan::plan(mode != 0, use_filter, prepass_done, call.dist != nullptr, ctx->dbg.filter_fused,
+                                                   ctx->dbg.filter_sync, ctx->filter.tot.force_sync);
+    int rc = at_pruned_image_claim(ctx, call);
+    if (rc) return rc;
+    rc = claim_prepass(ctx, call);
+    if (rc) return rc;
+    if (plan.image_up_front) {
+        rc = at_pruned_image_build(ctx, call);
+        if (rc) return rc;
+    }
+    if (plan.prepass_separate) {
+        rc = at_prune_prepass(ctx, call, call.n, call.order, call.hint_sorted, mode);
+        if (rc) return rc;
+    }
+    if (!plan.filter) return at_pruned_sweep_f32(ctx, call, call.n, call.order, call.hint_sorted);
+    // Stage 1: the fp16-split filter names the winner of every row whose runner-up is provably out of reach and lists
+    // the others; stage 2 redoes the listed rows in fp32.  Guess generators need neither the list nor stage 2.
+    int slot = AT_FILTER_RING;
+    rc = take_slot(ctx, plan, &slot);
+    if (rc) return rc;
+    rc = claim_filter(ctx, call);
+    if (rc) return rc;
+    rc = at_filter_sweep(ctx, call, plan.stage2 ? 1 : 0, plan.prepass_fused, plan.sweep_dist ? call.dist : nullptr, nullptr);
+    if (rc) return rc;
+    // (guess generators wrote an approximate distance themselves: it only orders the next visit)
+    if (plan.dist == exact_plan::DIST_FROM_TODO) rc = at_exact_dist_todo(ctx, call);
+    if (plan.dist == exact_plan::DIST_FROM_ROWS) rc = at_exact_dist_rows(ctx, call);
+    if (rc || !plan.stage2) return rc;
+    return plan.async_form ? finish_async(ctx, call, plan, slot) : finish_sync(ctx, call);
+}
+
+}  // namespace
+
+int at_filter_use_slot(at_ctx* ctx, int slot) {
+    AT_REQUIRE(slot >= 0 && slot <= AT_FILTER_RING, "at_filter_use_slot: slot %d out of range", slot);
+    at_filter_state& f = ctx->filter;
+    if (!f.host_misc) {
+        AT_HIP(hipHostMalloc(reinterpret_cast<void**>(&f.host_misc), (size_t)(AT_FILTER_RING + 1) * 128 * sizeof(unsigned),
+                             hipHostMallocDefault));
+        for (int s = 0; s <= AT_FILTER_RING; s++) f.ring[s].host_misc = f.host_misc + (size_t)s * 128;
+    }
+    at_filter_slot& fs = f.ring[slot];
+    if (!fs.copied) AT_HIP(hipEventCreateWithFlags(&fs.copied, hipEventDisableTiming));
+    fs.timed = 0;
+    f.slot = slot;
+    return AT_OK;
+}
+
+int at_filter_resolve_pending(at_ctx* ctx, bool wait_all) {
+    at_filter_state& f = ctx->filter;
+    while (f.count > 0) {
+        at_filter_slot& fs = f.ring[f.head];
+        if (wait_all) {
+            AT_HIP(hipEventSynchronize(fs.copied));
+        } else {
+            const hipError_t q = hipEventQuery(fs.copied);
+            if (q == hipErrorNotReady) break;   // an answer, not a failure (and the one code HIP does not keep pending)
+            AT_HIP(q);
+        }
+        exact_plan::fold_ring_slot(f.tot, fs.host_misc, fs.rows);
+        fold_timing(f, fs);
+        f.head = (f.head + 1) % AT_FILTER_RING;
+        f.count--;
+    }
+    return AT_OK;
+}
+
+extern "C" int at_assign_pruned_f32(at_ctx* ctx, const at_pruned_args* a, void* stream_) {
+    AT_REQUIRE(ctx && a, "at_assign_pruned_f32: ctx / args is null");
+    const int mode = a->guess_only ? 1 : 0;
+    at_exact_call call{};
+    call.x = a->x; call.n = a->n; call.d = a->d; call.c = a->c; call.k = a->k;
+    call.order = a->order; call.hint_sorted = a->hint_sorted; call.cperm = a->cperm; call.ng = a->ng; call.dmin = a->bounds;
+    call.ids = a->ids; call.dist = a->dist_or_null;
+    call.stream = (hipStream_t)stream_;
+    AT_REQUIRE(call.x && call.c && call.order && call.hint_sorted && call.cperm && (call.dmin || mode == 1) && call.ids,
+               "at_assign_pruned_f32: null pointer");
+    AT_REQUIRE(call.d == 64 || call.d == 128, "at_assign_pruned_f32: d must be 64 or 128");
+    AT_REQUIRE(call.k > 0 && grouped_sizes_ok(call.n, 20, call.d, call.k, call.ng),
+               "at_assign_pruned_f32: bad sizes n=%lld k=%d ng=%d", (long long)call.n, call.k, call.ng);
+    AT_REQUIRE(at_aligned16(call.x) && at_aligned16(call.c), "at_assign_pruned_f32: x and c must be 16-byte aligned");
+    AT_HIP(hipSetDevice(ctx->device));
+    ctx->img16_trusted = a->image_current != 0;  // consumed (and cleared) by the filter sweep
+    return exact_search(ctx, call, mode, a->prepass_done != 0, a->use_filter != 0);
+}
+
+// The pre-pass of at_assign_pruned_f32 on its own (per-row bound + per-tile group masks, kept in the
+// context's workspace): lets a caller time or overlap it separately, then call
+// at_assign_pruned_f32(..., prepass_done = 1) with the same arguments.
+extern "C" int at_prune_mask_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
+                                 const uint32_t* order, const uint32_t* hint_sorted, int ng, const float* dmin,
+                                 int mode, void* stream_) {
+    AT_REQUIRE(ctx && x && c && order && hint_sorted && (dmin || mode == 1), "at_prune_mask_f32: null pointer");
+    AT_REQUIRE(grouped_sizes_ok(n, 20, d, k, ng), "at_prune_mask_f32: bad sizes");
+    AT_HIP(hipSetDevice(ctx->device));
+    at_exact_call call{};
+    call.x = x; call.n = n; call.d = d; call.c = c; call.k = k;
+    call.order = order; call.hint_sorted = hint_sorted; call.ng = ng; call.dmin = dmin;
+    call.stream = (hipStream_t)stream_;
+    const int rc = claim_prepass(ctx, call);
+    if (rc) return rc;
+    return at_prune_prepass(ctx, call, n, order, hint_sorted, mode);
+}
+
+extern "C" int at_filter_stats(at_ctx* ctx, int64_t* rows, int64_t* listed, double* sweep_ms, int64_t* sweeps,
+                               int64_t* tiles, int64_t* refined, int reset) {
+    AT_REQUIRE(ctx && rows && listed, "at_filter_stats: bad arguments");
+    const int rcp = at_filter_resolve_pending(ctx, true);
+    if (rcp) return rcp;
+    at_filter_state& f = ctx->filter;
+    *rows = f.tot.rows;
+    *listed = f.tot.listed;
+    if (sweep_ms) *sweep_ms = f.ms;
+    if (sweeps) *sweeps = f.launches;
+    if (tiles) *tiles = f.tot.tiles;
+    if (refined) *refined = f.tot.refined;
+    if (reset) {
+        f.tot.rows = f.tot.listed = f.tot.tiles = f.tot.refined = f.launches = 0;
+        f.ms = 0.0;
+    }
+    return AT_OK;
+}
+
+// Test hook: pre-pass + stage 1 only.  approx[2i] = approximate |c|^2 - 2 x.c of row i's winner,
+// approx[2i+1] = gap to the runner-up; ids = the winners; *listed = rows the filter would hand to the
+// fp32 sweep; tau_ab[0..1] = the coefficients of the acceptance threshold tau = a (|x|^2 + max|c|^2) + b.
+extern "C" int at_filter_probe_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
+                                   const uint32_t* order, const uint32_t* hint_sorted, const int32_t* cperm, int ng,
+                                   const float* dmin, int64_t* ids, float* approx, int64_t* listed, void* stream_) {
+    AT_REQUIRE(ctx && x && c && order && hint_sorted && cperm && dmin && ids && approx && listed,
+               "at_filter_probe_f32: null pointer");
+    AT_REQUIRE(k > 0 && grouped_sizes_ok(n, 20, d, k, ng), "at_filter_probe_f32: bad sizes");
+    AT_HIP(hipSetDevice(ctx->device));
+    at_exact_call call{};
+    call.x = x; call.n = n; call.d = d; call.c = c; call.k = k;
+    call.order = order; call.hint_sorted = hint_sorted; call.cperm = cperm; call.ng = ng; call.dmin = dmin;
+    call.ids = ids;
+    call.stream = (hipStream_t)stream_;
+    int rc = claim_prepass(ctx, call);
+    if (rc) return rc;
+    rc = claim_filter(ctx, call);
+    if (rc) return rc;
+    rc = at_prune_prepass(ctx, call, n, order, hint_sorted, 0);
+    if (rc) return rc;
+    rc = at_filter_use_slot(ctx, AT_FILTER_RING);   // (a call outside the ring: the spare slot)
+    if (rc) return rc;
+    rc = at_filter_sweep(ctx, call, 1, false, nullptr, approx);
+    if (rc) return rc;
+    unsigned cnts[AT_AMB_SUBLISTS];
+    AT_HIP(hipMemcpyAsync(cnts, call.misc + 64, sizeof cnts, hipMemcpyDeviceToHost, call.stream));
+    AT_HIP(hipStreamSynchronize(call.stream));
+    int64_t cnt = 0;
+    for (unsigned s = 0; s < AT_AMB_SUBLISTS; s++) cnt += cnts[s];
+    *listed = cnt;
+    return AT_OK;
+}
+
+// Guess generator without a pre-sort, for rows whose own order is coherent (the frames of a clip follow
+// one another): nearest of the ng group means -> the groups its neighbour table names -> best centroid
+// among them, in one launch.  ids are guesses (feed at_visit_order_f32 / at_assign_pruned_f32), dist (optional)
+// approximate distances.
+extern "C" int at_assign_coarse_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
+                                    const int32_t* cperm, int ng, const float* means, const uint32_t* gnbr,
+                                    int64_t* ids, float* dist, void* stream_) {
+    AT_REQUIRE(ctx && x && c && cperm && means && gnbr && ids, "at_assign_coarse_f32: null pointer");
+    AT_REQUIRE(k > 0 && grouped_sizes_ok(n, 1, d, k, ng), "at_assign_coarse_f32: bad sizes");
+    AT_REQUIRE(at_aligned16(x) && at_aligned16(c) && at_aligned16(means), "at_assign_coarse_f32: pointers must be 16-byte aligned");
+    AT_HIP(hipSetDevice(ctx->device));
+    return at_filter_coarse(ctx, x, n, d, c, k, cperm, ng, means, gnbr, ids, dist, (hipStream_t)stream_);
+}

@@ -1126,26 +1126,36 @@ void filter_rho(int d, float* rho_a, float* rho_b) {
 
 size_t at_filter_group_bytes(int d) { return group_bytes(d); }
 
-int at_amb_compact(at_ctx* ctx, const unsigned* misc, unsigned amb_cap, const uint32_t* list, const uint32_t* aux,
-                   uint32_t* list_out, uint32_t* aux_out, hipStream_t stream) {
+int at_amb_compact(at_ctx* ctx, const at_exact_call& call) {
     (void)ctx;
-    AT_LAUNCH(amb_compact_kernel, dim3(256), dim3(WG), 0, stream, misc, amb_cap, list, aux, list_out, aux_out);
+    AT_LAUNCH(amb_compact_kernel, dim3(256), dim3(WG), 0, call.stream, call.misc, call.amb_cap, call.list, call.aux,
+              call.sorted, call.order_amb);
     return AT_OK;
 }
 
-// Stage 1: image + sweep.  misc (device, 2 words) receives max|c|^2 and the number of listed rows;
-// amb_list receives their visiting positions (unordered).
-int at_filter_sweep(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const uint32_t* order,
-                    const int32_t* cperm, int ng, const float* bd, const uint32_t* mask, int ngw, int collect,
-                    int64_t* ids, unsigned* misc, uint32_t* amb_list, uint32_t* amb_aux, float* approx_out,
-                    const uint32_t* fuse_hint_sorted, const float* fuse_dmin, float* fuse_bd_out, float* fuse_dist_out,
-                    unsigned amb_cap, hipStream_t stream) {
+// Stage 1: image + sweep.  call.misc (device) receives max|c|^2, the statistics and the sub-list lengths;
+// call.list / call.aux receive the visiting positions of the listed rows (unordered).
+int at_filter_sweep(at_ctx* ctx, const at_exact_call& call, int collect, bool fused_prepass, float* dist_out,
+                    float* approx_out) {
+    const float *x = call.x, *c = call.c, *bd = call.bd;
+    const int64_t n = call.n;
+    const int d = call.d, k = call.k, ng = call.ng, ngw = call.ngw;
+    const uint32_t *order = call.order, *mask = call.mask;
+    const int32_t* cperm = call.cperm;
+    int64_t* ids = call.ids;
+    unsigned* misc = call.misc;
+    uint32_t *amb_list = call.list, *amb_aux = call.aux;
+    const unsigned amb_cap = call.amb_cap;
+    hipStream_t stream = call.stream;
     unsigned char* img = static_cast<unsigned char*>(at_ws(ctx, WS_CENT_IMG16, group_bytes(d) * (size_t)ng, stream));
     if (!img) return AT_E_NOMEM;
     // fused pre-pass (exact calls only): the sweep computes the guess distances and its own group masks
-    const bool fused = fuse_hint_sorted && fuse_dmin && fuse_bd_out && collect;
-    FusedPrepass fp{fuse_hint_sorted, c, fuse_dmin, fuse_bd_out, fuse_dist_out, nullptr, k};  // (guess generators use dist_out only)
+    const bool fused = fused_prepass && collect;
+    FusedPrepass fp{nullptr, c, nullptr, nullptr, dist_out, nullptr, k};  // (guess generators use dist_out only)
     if (fused) {
+        fp.hint_sorted = call.hint_sorted;
+        fp.dmin = call.dmin;
+        fp.bd_out = call.bd;
         const bool fresh = ctx->ws[WS_PRUNE_STATS] == nullptr;
         fp.stats = static_cast<unsigned long long*>(at_ws(ctx, WS_PRUNE_STATS, 4096, stream));
         if (!fp.stats) return AT_E_NOMEM;
@@ -1156,18 +1166,16 @@ int at_filter_sweep(at_ctx* ctx, const float* x, int64_t n, int d, const float* 
     const bool reuse = ctx->img16_trusted && ctx->img16_c == c && ctx->img16_cperm == cperm && ctx->img16_k == k &&
                        ctx->img16_d == d && ctx->img16_ng == ng && misc == ctx->img16_misc;
     ctx->img16_trusted = 0;
-    const int misc_was_clean = ctx->img16_misc_clean;
-    ctx->img16_misc_clean = 0;
-    (void)misc_was_clean;
     if (reuse) {
         // statistics and sub-list lengths behind max|c|^2: at_group_min_dist_f16 cleared them with the same memset that
         // cleared max|c|^2 (an odd-sized memset from misc + 1 costs two fill launches)
-        if (!misc_was_clean) AT_HIP(hipMemsetAsync(misc + 1, 0, 127 * sizeof(unsigned), stream));
+        if (!ctx->img16_misc_clean) AT_HIP(hipMemsetAsync(misc + 1, 0, 127 * sizeof(unsigned), stream));
     } else {
         ctx->img16_c = nullptr;
         AT_HIP(hipMemsetAsync(misc, 0, 128 * sizeof(unsigned), stream));  // max|c|^2, statistics, sub-list lengths
         AT_LAUNCH(prep_centroids_f16_kernel, dim3(ng), dim3(WG), 0, stream, c, k, d, cperm, img, misc);
     }
+    ctx->img16_misc_clean = 0;   // (this sweep counts into them)
     float ta = 0.0f, tb = 0.0f, ra = 0.0f, rb = 0.0f;
     filter_tau(d, &ta, &tb);
     filter_rho(d, &ra, &rb);
@@ -1194,7 +1202,7 @@ int at_filter_sweep(at_ctx* ctx, const float* x, int64_t n, int d, const float* 
     // exact calls under the switch filter_timing (bench.py): two timing events around the kernel, read by
     // at_filter_resolve_pending / the synchronous form once the call's statistics have arrived.  The product leaves
     // the switch off: no event is recorded and none is read.
-    at_filter_slot& tslot = ctx->fring[(ctx->filter_slot >= 0 && ctx->filter_slot <= AT_FILTER_RING) ? ctx->filter_slot : AT_FILTER_RING];
+    at_filter_slot& tslot = ctx->filter.ring[(ctx->filter.slot >= 0 && ctx->filter.slot <= AT_FILTER_RING) ? ctx->filter.slot : AT_FILTER_RING];
     const bool timed = collect && ctx->dbg.filter_timing != 0;
     tslot.timed = 0;
     if (timed) {
@@ -1203,34 +1211,26 @@ int at_filter_sweep(at_ctx* ctx, const float* x, int64_t n, int d, const float* 
                 AT_HIP(hipEventCreateWithFlags(&tslot.ev[i], hipEventDisableSystemFence));
         AT_HIP(hipEventRecord(tslot.ev[0], stream));
     }
-#define AT_FILTER_LAUNCH(DD, NBB, GG, FF, GRID)                                                                      \
-    AT_LAUNCH((assign_f16filter_kernel<DD, NBB, GG, FF>), GRID, dim3(64), 0, stream, x, (long)n, img, ng, order, \
+#define AT_FILTER_LAUNCH(DD, NBB, GG, FF, WW, GRID)                                                                   \
+    AT_LAUNCH((assign_f16filter_kernel<DD, NBB, GG, FF, WW>), GRID, dim3(64), 0, stream, x, (long)n, img, ng, order, \
                        bd, mask, ngw, misc, ta, tb, ra, rb, screen, collect, reinterpret_cast<long*>(ids), amb_list,      \
                        amb_aux, approx_out, fp, blk_stats, amb_cap)
     // exact calls (collect) and guess generators are separate instantiations: the guess path's code
     // would otherwise cost the exact sweep registers it does not have
     const dim3 grid64((unsigned)((n + 63) / 64));
     if (d == 128) {  // two tiles per wave: the fragment sets of d = 128 leave no registers for four
-        if (fused) AT_FILTER_LAUNCH(128, 2, false, true, grid64);
-        else if (collect) AT_FILTER_LAUNCH(128, 2, false, false, grid64);
-        else AT_FILTER_LAUNCH(128, 2, true, false, grid64);
+        if (fused) AT_FILTER_LAUNCH(128, 2, false, true, 2, grid64);
+        else if (collect) AT_FILTER_LAUNCH(128, 2, false, false, 2, grid64);
+        else AT_FILTER_LAUNCH(128, 2, true, false, 2, grid64);
     } else if (NB == 4) {
-        if (fused) AT_FILTER_LAUNCH(64, 4, false, true, grid);
-        else if (collect) AT_FILTER_LAUNCH(64, 4, false, false, grid);
-        else AT_FILTER_LAUNCH(64, 4, true, false, grid);
-    } else if (one_tile) {
-        AT_LAUNCH((assign_f16filter_kernel<64, 1, false, true, 4>), grid, dim3(64), 0, stream, x, (long)n, img, ng,
-                           order, bd, mask, ngw, misc, ta, tb, ra, rb, screen, collect, reinterpret_cast<long*>(ids),
-                           amb_list, amb_aux, approx_out, fp, blk_stats, amb_cap);
-    } else {
-        if (wps3) {
-            AT_LAUNCH((assign_f16filter_kernel<64, 2, false, true, 3>), grid, dim3(64), 0, stream, x, (long)n, img, ng,
-                               order, bd, mask, ngw, misc, ta, tb, ra, rb, screen, collect, reinterpret_cast<long*>(ids),
-                               amb_list, amb_aux, approx_out, fp, blk_stats, amb_cap);
-        } else if (fused) AT_FILTER_LAUNCH(64, 2, false, true, grid);
-        else if (collect) AT_FILTER_LAUNCH(64, 2, false, false, grid);
-        else AT_FILTER_LAUNCH(64, 2, true, false, grid);
-    }
+        if (fused) AT_FILTER_LAUNCH(64, 4, false, true, 2, grid);
+        else if (collect) AT_FILTER_LAUNCH(64, 4, false, false, 2, grid);
+        else AT_FILTER_LAUNCH(64, 4, true, false, 2, grid);
+    } else if (one_tile) AT_FILTER_LAUNCH(64, 1, false, true, 4, grid);
+    else if (wps3) AT_FILTER_LAUNCH(64, 2, false, true, 3, grid);
+    else if (fused) AT_FILTER_LAUNCH(64, 2, false, true, 2, grid);
+    else if (collect) AT_FILTER_LAUNCH(64, 2, false, false, 2, grid);
+    else AT_FILTER_LAUNCH(64, 2, true, false, 2, grid);
 #undef AT_FILTER_LAUNCH
     if (timed) {
         AT_HIP(hipEventRecord(tslot.ev[1], stream));
@@ -1242,77 +1242,73 @@ int at_filter_sweep(at_ctx* ctx, const float* x, int64_t n, int d, const float* 
     return AT_OK;
 }
 
-int at_exact_dist_rows(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const int64_t* ids,
-                       float* dist, const uint32_t* order, const uint32_t* hint_sorted, const float* bd,
-                       hipStream_t stream) {
+int at_exact_dist_rows(at_ctx* ctx, const at_exact_call& call) {
     (void)ctx;
-    const dim3 grid((unsigned)((n + WG - 1) / WG));
-    if (order && hint_sorted && bd) {  // guesses with their pre-pass distances available
-        if (d == 64)
-            AT_LAUNCH(exact_dist_visit_kernel<64>, grid, dim3(WG), 0, stream, x, (long)n, c, k, order,
-                               hint_sorted, bd, reinterpret_cast<const long*>(ids), dist);
+    const dim3 grid((unsigned)((call.n + WG - 1) / WG));
+    if (call.order && call.hint_sorted && call.bd) {  // guesses with their pre-pass distances available
+        if (call.d == 64)
+            AT_LAUNCH(exact_dist_visit_kernel<64>, grid, dim3(WG), 0, call.stream, call.x, (long)call.n, call.c, call.k,
+                      call.order, call.hint_sorted, call.bd, reinterpret_cast<const long*>(call.ids), call.dist);
         else
-            AT_LAUNCH(exact_dist_visit_kernel<128>, grid, dim3(WG), 0, stream, x, (long)n, c, k, order,
-                               hint_sorted, bd, reinterpret_cast<const long*>(ids), dist);
+            AT_LAUNCH(exact_dist_visit_kernel<128>, grid, dim3(WG), 0, call.stream, call.x, (long)call.n, call.c, call.k,
+                      call.order, call.hint_sorted, call.bd, reinterpret_cast<const long*>(call.ids), call.dist);
         return AT_OK;
     }
-    if (d == 64)
-        AT_LAUNCH(exact_dist_rows_kernel<64>, grid, dim3(WG), 0, stream, x, (long)n, c, k,
-                           reinterpret_cast<const long*>(ids), dist);
+    if (call.d == 64)
+        AT_LAUNCH(exact_dist_rows_kernel<64>, grid, dim3(WG), 0, call.stream, call.x, (long)call.n, call.c, call.k,
+                  reinterpret_cast<const long*>(call.ids), call.dist);
     else
-        AT_LAUNCH(exact_dist_rows_kernel<128>, grid, dim3(WG), 0, stream, x, (long)n, c, k,
-                           reinterpret_cast<const long*>(ids), dist);
+        AT_LAUNCH(exact_dist_rows_kernel<128>, grid, dim3(WG), 0, call.stream, call.x, (long)call.n, call.c, call.k,
+                  reinterpret_cast<const long*>(call.ids), call.dist);
     return AT_OK;
 }
 
 // Sorts the m_valid listed positions (visiting order keeps the tiles of the redo pass coherent) and
-// expands them to m >= m_valid entries (the fp32 sweep wants at least 20 rows).
-int at_filter_gather_ambiguous(at_ctx* ctx, uint32_t* amb_list, uint32_t* amb_sorted, int64_t m_valid, int64_t m,
-                               const uint32_t* order, const int64_t* ids, uint32_t* order_amb, uint32_t* hint_amb,
-                               hipStream_t stream) {
+// expands them to m >= m_valid entries (the fp32 sweep wants at least 20 rows): call.list -> call.sorted ->
+// call.order_amb / call.hint_amb.
+int at_filter_gather_ambiguous(at_ctx* ctx, const at_exact_call& call, int64_t m_valid, int64_t m) {
+    hipStream_t stream = call.stream;
     size_t tmp_bytes = 0;
-    AT_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, amb_list, amb_sorted, (size_t)m_valid, 0, 32, stream));
+    AT_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, call.list, call.sorted, (size_t)m_valid, 0, 32, stream));
     void* tmp = at_ws(ctx, WS_SORT_TMP, tmp_bytes, stream);
     if (!tmp) return AT_E_NOMEM;
-    AT_HIP(rocprim::radix_sort_keys(tmp, tmp_bytes, amb_list, amb_sorted, (size_t)m_valid, 0, 32, stream));
-    AT_LAUNCH(gather_ambiguous_kernel, dim3((unsigned)((m + WG - 1) / WG)), dim3(WG), 0, stream, amb_sorted,
-                       (long)m, (long)m_valid, order, reinterpret_cast<const long*>(ids), order_amb, hint_amb);
+    AT_HIP(rocprim::radix_sort_keys(tmp, tmp_bytes, call.list, call.sorted, (size_t)m_valid, 0, 32, stream));
+    AT_LAUNCH(gather_ambiguous_kernel, dim3((unsigned)((m + WG - 1) / WG)), dim3(WG), 0, stream, call.sorted,
+                       (long)m, (long)m_valid, call.order, reinterpret_cast<const long*>(call.ids), call.order_amb, call.hint_amb);
     return AT_OK;
 }
 
-
-// Stage 2 for short lists: one workgroup per listed row (see exact_rows_kernel).
-int at_filter_redo_rows(at_ctx* ctx, const float* x, int d, const float* c, int k, const uint32_t* list, int64_t m,
-                        const uint32_t* order, const int32_t* cperm, const float* dmin, int ng, const unsigned* misc,
-                        const uint32_t* aux, int64_t* ids, float* dist, const unsigned* count_dev, unsigned amb_cap,
-                        hipStream_t stream) {
+// Stage 2 for short lists: one workgroup per listed row (see exact_rows_kernel); the kernels read the sub-list
+// lengths on the device (call.misc + 64).
+int at_filter_redo_rows(at_ctx* ctx, const at_exact_call& call, int64_t m) {
     (void)ctx;
-    if (m <= 0) return AT_OK;   // m = list length, or (with count_dev) the number of workgroups to launch
-    AT_REQUIRE(ng <= 512, "at_filter_redo_rows: ng > 512");
-    if (d == 64)
-        AT_LAUNCH(exact_rows_kernel<64>, dim3((unsigned)m), dim3(WG), 0, stream, x, c, k, list, order, cperm, dmin,
-                           ng, misc, aux, reinterpret_cast<long*>(ids), dist, count_dev, amb_cap);
+    if (m <= 0) return AT_OK;   // m = list length, or the number of workgroups to launch
+    AT_REQUIRE(call.ng <= 512, "at_filter_redo_rows: ng > 512");
+    if (call.d == 64)
+        AT_LAUNCH(exact_rows_kernel<64>, dim3((unsigned)m), dim3(WG), 0, call.stream, call.x, call.c, call.k, call.list, call.order,
+                  call.cperm, call.dmin, call.ng, call.misc, call.aux, reinterpret_cast<long*>(call.ids), call.dist, call.misc + 64,
+                  call.amb_cap);
     else
-        AT_LAUNCH(exact_rows_kernel<128>, dim3((unsigned)m), dim3(WG), 0, stream, x, c, k, list, order, cperm,
-                           dmin, ng, misc, aux, reinterpret_cast<long*>(ids), dist, count_dev, amb_cap);
+        AT_LAUNCH(exact_rows_kernel<128>, dim3((unsigned)m), dim3(WG), 0, call.stream, call.x, call.c, call.k, call.list, call.order,
+                  call.cperm, call.dmin, call.ng, call.misc, call.aux, reinterpret_cast<long*>(call.ids), call.dist, call.misc + 64,
+                  call.amb_cap);
     return AT_OK;
 }
 
 // The distance pass and the redo of the listed rows behind a fused sweep, one launch (asynchronous exact calls).
-int at_filter_finish(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const uint32_t* list, int64_t redo_wgs,
-                     const uint32_t* order, const int32_t* cperm, const float* dmin, int ng, const unsigned* misc,
-                     const uint32_t* aux, int64_t* ids, float* dist, const unsigned* count_dev, unsigned amb_cap,
-                     hipStream_t stream) {
+int at_filter_finish(at_ctx* ctx, const at_exact_call& call, int64_t redo_wgs) {
     (void)ctx;
-    AT_REQUIRE(ng <= 512 && dist && redo_wgs > 0, "at_filter_finish: bad arguments");
-    const unsigned todo_blocks = (unsigned)((n + WG - 1) / WG);
+    AT_REQUIRE(call.ng <= 512 && call.dist && redo_wgs > 0, "at_filter_finish: bad arguments");
+    const unsigned todo_blocks = (unsigned)((call.n + WG - 1) / WG);
     const dim3 grid(todo_blocks + (unsigned)redo_wgs);
-    if (d == 64)
-        AT_LAUNCH(exact_finish_kernel<64>, grid, dim3(WG), 0, stream, todo_blocks, (long)n, x, c, k, list, order, cperm, dmin, ng,
-                  misc, aux, reinterpret_cast<long*>(ids), dist, count_dev, amb_cap);
+    if (call.d == 64)
+        AT_LAUNCH(exact_finish_kernel<64>, grid, dim3(WG), 0, call.stream, todo_blocks, (long)call.n, call.x, call.c, call.k,
+                  call.list, call.order, call.cperm, call.dmin, call.ng, call.misc, call.aux, reinterpret_cast<long*>(call.ids),
+                  call.dist, call.misc + 64, call.amb_cap);
     else
-        AT_LAUNCH(exact_finish_kernel<128>, grid, dim3(WG), 0, stream, todo_blocks, (long)n, x, c, k, list, order, cperm, dmin, ng,
-                  misc, aux, reinterpret_cast<long*>(ids), dist, count_dev, amb_cap);
+        AT_LAUNCH(exact_finish_kernel<128>, grid, dim3(WG), 0, call.stream, todo_blocks, (long)call.n, call.x, call.c, call.k,
+                  call.list, call.order, call.cperm, call.dmin, call.ng, call.misc, call.aux, reinterpret_cast<long*>(call.ids),
+                  call.dist, call.misc + 64, call.amb_cap);
     return AT_OK;
 }
 
@@ -1348,16 +1344,15 @@ int at_group_min_dist_f16(at_ctx* ctx, const float* c, int k, int d, const int32
 }
 
 // Completes dist after a fused sweep that was given dist_out (see exact_dist_todo_kernel).
-int at_exact_dist_todo(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const int64_t* ids,
-                       float* dist, hipStream_t stream) {
+int at_exact_dist_todo(at_ctx* ctx, const at_exact_call& call) {
     (void)ctx;
-    const dim3 grid((unsigned)((n + WG - 1) / WG));
-    if (d == 64)
-        AT_LAUNCH(exact_dist_todo_kernel<64>, grid, dim3(WG), 0, stream, x, (long)n, c, k,
-                           reinterpret_cast<const long*>(ids), dist);
+    const dim3 grid((unsigned)((call.n + WG - 1) / WG));
+    if (call.d == 64)
+        AT_LAUNCH(exact_dist_todo_kernel<64>, grid, dim3(WG), 0, call.stream, call.x, (long)call.n, call.c, call.k,
+                  reinterpret_cast<const long*>(call.ids), call.dist);
     else
-        AT_LAUNCH(exact_dist_todo_kernel<128>, grid, dim3(WG), 0, stream, x, (long)n, c, k,
-                           reinterpret_cast<const long*>(ids), dist);
+        AT_LAUNCH(exact_dist_todo_kernel<128>, grid, dim3(WG), 0, call.stream, call.x, (long)call.n, call.c, call.k,
+                  reinterpret_cast<const long*>(call.ids), call.dist);
     return AT_OK;
 }
 
@@ -1370,7 +1365,7 @@ __global__ void __launch_bounds__(WG) iota_pad_kernel(int32_t* __restrict__ perm
 
 // Guess generator for rows whose own order is coherent (consecutive frames of clips): per 32-row tile the
 // nearest of the ng group means decides, through the neighbour table gnbr [ng][ceil(ng/32)], which groups
-// of centroids are searched -- one launch, rows read once (assign.hip: at_assign_coarse_f32).
+// of centroids are searched -- one launch, rows read once (exact_search.cpp: at_assign_coarse_f32).
 int at_filter_coarse(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, const int32_t* cperm, int ng,
                      const float* means, const uint32_t* gnbr, int64_t* ids, float* dist, hipStream_t stream) {
     const int ngm = (ng + 31) / 32;              // groups of the means image

@@ -151,7 +151,7 @@ int at_create(int device, at_ctx** out) {
     if (!c) return at_fail(AT_E_NOMEM, "at_create: out of host memory");
     std::memset(c, 0, sizeof *c);
     c->device = device;
-    c->filter_slot = AT_FILTER_RING;
+    c->filter.slot = AT_FILTER_RING;
     c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     for (const DebugField& f : kDebugFields) {   // the only place the environment is read
         const char* e = std::getenv(f.env);
@@ -174,7 +174,7 @@ void at_destroy(at_ctx* ctx) {
     for (int i = 0; i < 2; i++)
         if (ctx->side_ev[i]) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->side_ev[i]));
     for (int s = 0; s <= AT_FILTER_RING; s++) {
-        at_filter_slot& fs = ctx->fring[s];
+        at_filter_slot& fs = ctx->filter.ring[s];
         if (fs.copied) (void)AT_HIP_TOLERATE(hipEventDestroy(fs.copied));
         for (int i = 0; i < 2; i++)
             if (fs.ev[i]) (void)AT_HIP_TOLERATE(hipEventDestroy(fs.ev[i]));
@@ -187,7 +187,7 @@ void at_destroy(at_ctx* ctx) {
     if (ctx->sil_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sil_ev));
     if (ctx->knn_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->knn_ev));
     if (ctx->ap_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->ap_ev));
-    if (ctx->filter_host_misc) (void)AT_HIP_TOLERATE(hipHostFree(ctx->filter_host_misc));
+    if (ctx->filter.host_misc) (void)AT_HIP_TOLERATE(hipHostFree(ctx->filter.host_misc));
     at_logmel_tables_clear(&ctx->lm_fb);
     at_logmel_tables_clear(&ctx->lm_any);
     (void)AT_HIP_TOLERATE(hipSetDevice(prev));

@@ -1,5 +1,5 @@
 // prune.hip -- the bookkeeping that lets a Lloyd iteration skip most of the -2XC^T work without
-// changing a single output bit (used by at_assign_pruned_f32, assign.hip).
+// changing a single output bit (used by at_assign_pruned_f32, exact_search.cpp).
 //
 // Replaces nothing in the reference by itself: it accelerates the search inside
 // faiss.Kmeans.train (processors/cluster_creator.py:54-56 of danavery/audio-tokens) from the second
@@ -312,33 +312,31 @@ __global__ __launch_bounds__(256) void group_neighbours_kernel(const float* __re
 
 }  // namespace
 
-// ---- entry points used by assign.hip and the C ABI -------------------------------------------
-int at_prune_prepass(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
-                     const uint32_t* order, const uint32_t* hint_sorted, const float* dmin, int ng,
-                     float* bd_out, uint32_t* mask, int ngw, int mode, hipStream_t stream) {
+// ---- entry points used by exact_search.cpp and the C ABI -------------------------------------------
+int at_prune_prepass(at_ctx* ctx, const at_exact_call& call, int64_t n, const uint32_t* order, const uint32_t* hint_sorted,
+                     int mode) {
+    hipStream_t stream = call.stream;
+    const long waves = (n + 63) / 64;
+    const dim3 grid((unsigned)((waves + WG / 64 - 1) / (WG / 64)));
     if (mode == 1) {  // hint_sorted holds group ids: each tile needs just those groups (+ neighbours)
-        const long waves1 = (n + 63) / 64;
-        AT_LAUNCH(group_only_mask_kernel, dim3((unsigned)((waves1 + WG / 64 - 1) / (WG / 64))), dim3(WG), 0,
-                           stream, (long)n, hint_sorted, ng, reinterpret_cast<const uint32_t*>(dmin), bd_out, mask,
-                           ngw);
+        AT_LAUNCH(group_only_mask_kernel, grid, dim3(WG), 0, stream, (long)n, hint_sorted, call.ng,
+                  reinterpret_cast<const uint32_t*>(call.dmin), call.bd, call.mask, call.ngw);
         return AT_OK;
     }
     unsigned* cnmax = static_cast<unsigned*>(at_ws(ctx, WS_REDUCE, 1024 * sizeof(double), stream));
     if (!cnmax) return AT_E_NOMEM;
     AT_HIP(hipMemsetAsync(cnmax, 0, sizeof(unsigned), stream));
-    AT_LAUNCH(max_sqnorm_kernel, dim3((k + WG - 1) / WG), dim3(WG), 0, stream, c, k, d, cnmax);
-    const long waves = (n + 63) / 64;
-    const dim3 grid((unsigned)((waves + WG / 64 - 1) / (WG / 64)));
+    AT_LAUNCH(max_sqnorm_kernel, dim3((call.k + WG - 1) / WG), dim3(WG), 0, stream, call.c, call.k, call.d, cnmax);
     const bool fresh = ctx->ws[WS_PRUNE_STATS] == nullptr;
     unsigned long long* stats = static_cast<unsigned long long*>(at_ws(ctx, WS_PRUNE_STATS, 4096, stream));
     if (!stats) return AT_E_NOMEM;
     if (fresh) AT_HIP(hipMemsetAsync(stats, 0, 4096, stream));
-    if (d == 64)
-        AT_LAUNCH(prune_mask_kernel<64>, grid, dim3(WG), 0, stream, x, (long)n, c, k, order, hint_sorted,
-                           dmin, ng, cnmax, bd_out, mask, ngw, stats);
+    if (call.d == 64)
+        AT_LAUNCH(prune_mask_kernel<64>, grid, dim3(WG), 0, stream, call.x, (long)n, call.c, call.k, order, hint_sorted,
+                  call.dmin, call.ng, cnmax, call.bd, call.mask, call.ngw, stats);
     else
-        AT_LAUNCH(prune_mask_kernel<128>, grid, dim3(WG), 0, stream, x, (long)n, c, k, order, hint_sorted,
-                           dmin, ng, cnmax, bd_out, mask, ngw, stats);
+        AT_LAUNCH(prune_mask_kernel<128>, grid, dim3(WG), 0, stream, call.x, (long)n, call.c, call.k, order, hint_sorted,
+                  call.dmin, call.ng, cnmax, call.bd, call.mask, call.ngw, stats);
     return AT_OK;
 }
 

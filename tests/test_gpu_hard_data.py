@@ -8,11 +8,11 @@ rows listed for the redo) leave most of the redo machinery idle.  These tests fe
 1. noise-dominated clips (synth_clips(noisy=True), bench.py's `hard_workload`) through the whole pipeline, against the
    oracle at small sizes and against the plain dense fp32 sweeps at the full Lloyd shape;
 2. data scaled down far enough that the filter's absolute error term lists every row, which walks a filtered exact call
-   through each of its four ways to finish (launch_pruned in csrc/assign.hip):
+   through each of its four ways to finish (csrc/exact_search.cpp; the route is exact_plan::plan in csrc/exact_plan.h):
      path 1  asynchronous form, short list: the redo kernels read the list length on the device
      path 2  asynchronous form, a list longer than n/16: the same kernels stride over it; the call's statistics then
-             switch the context to the synchronous form (filter_force_sync)
-     path 3  synchronous form, short list: exact_rows_kernel on the contiguous list; clears filter_force_sync
+             switch the context to the synchronous form (force_sync of the filter's totals)
+     path 3  synchronous form, short list: exact_rows_kernel on the contiguous list; clears force_sync
      path 4  synchronous form, long list: the listed rows gathered (padded to at least 64), a fresh pre-pass and the
              fp32 MFMA pruned sweep over them
    and the fp16-range edge of the filter's input check (|v|^2 < 2^30);
@@ -57,7 +57,7 @@ def _oracle_pipeline(oracle, frames, T, n_train, k, niter, batch_clips):
 
 
 def _settle(be, xt, ct, order, cperm, dmin):
-    """A filtered exact call on data the filter settles, then the statistics: leaves filter_force_sync cleared (a short
+    """A filtered exact call on data the filter settles, then the statistics: leaves force_sync cleared (a short
     list clears it in the synchronous form and never sets it in the asynchronous one), whatever came before."""
     be.assign_pruned(xt, ct, order, cperm, dmin, filter=True)
     rows, listed = be.filter_stats()

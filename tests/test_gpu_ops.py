@@ -747,6 +747,49 @@ def test_ab_switches_leave_the_bits_alone(be, oracle, switches, sw):
     assert np.array_equal(ids.cpu().numpy(), ids_o) and np.array_equal(bits(dis.cpu().numpy()), bits(dis_o))
 
 
+_PARTIAL_TILES = {}
+
+
+def _partial_tiles_case(be, oracle):
+    """d = 128, 65 tiles of 32 rows plus one row (the last tile and the last 64-row workgroup are partial), 1000 centroids
+    (a partly empty last group), 80 % of the guesses right; the oracle's answer is computed once."""
+    if not _PARTIAL_TILES:
+        rng = np.random.default_rng(2081)
+        n, d, k = 2081, 128, 1000
+        centers = _unit_rows(rng, k, d, oracle)
+        x = oracle.l2norm_rows((centers[rng.integers(0, k, n)] + 0.05 * rng.standard_normal((n, d))).astype(np.float32))
+        c = oracle.l2norm_rows((centers + 0.01 * rng.standard_normal((k, d))).astype(np.float32))
+        ids_o, dis_o = oracle.assign(x, c)
+        guess = np.where(rng.random(n) < 0.8, ids_o, rng.integers(0, k, n))
+        _PARTIAL_TILES.update(x=x, c=c, ids=ids_o, dis=dis_o, guess=guess, cperm=be.group_rows_kd(c))
+    return _PARTIAL_TILES
+
+
+@pytest.mark.parametrize("sw", [{}, {"filter_fused": 0}, {"filter_sync": 1}, {"filter": 0}])
+def test_exact_routes_at_d128_with_partial_tiles(be, oracle, switches, sw):
+    """The routes of an exact call (fused or separate pre-pass, asynchronous or synchronous form, no filter at all), with
+    and without distances, where every launch has a partial last tile: ids and distance bits of the oracle, and the
+    filter's statistics account for every row exactly once."""
+    case = _partial_tiles_case(be, oracle)
+    n, k = case["x"].shape[0], case["c"].shape[0]
+    switches(**sw)
+    xt, ct = be._f32(case["x"]), be._f32(case["c"])
+    cperm = be.from_host(case["cperm"])
+    dmin = be.group_min_dist(ct, cperm)
+    order = be.visit_order(torch.from_numpy(case["guess"]).to(be.device).contiguous(), None, k)
+    filtered = sw.get("filter", 1) != 0
+    be.filter_stats()                                                       # (reads and resets the totals)
+    for want_dist in (True, False):
+        ids, dis = be.assign_pruned(xt, ct, order, cperm, dmin, want_dist=want_dist)
+        assert np.array_equal(ids.cpu().numpy(), case["ids"]), (sw, want_dist)
+        if want_dist:
+            assert np.array_equal(bits(dis.cpu().numpy()), bits(case["dis"])), sw
+        else:
+            assert dis is None
+        if filtered:
+            assert be.filter_stats()[0] == n, (sw, want_dist)
+
+
 @pytest.mark.parametrize("ng,d,nnb", [(256, 64, 8), (256, 64, 4), (37, 128, 4), (3, 64, 8), (512, 64, 8)])
 def test_group_neighbours_names_the_nearest_means(be, ng, d, nnb):
     """The neighbour table (a heuristic input, it never decides a result) names g itself and the groups
