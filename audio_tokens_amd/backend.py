@@ -1072,20 +1072,54 @@ class HipBackend(HostHelpers):
         copied) -> (ap float64 [c], NaN for the classes without positives; n_pos int64 [c]; map_pair float64 [2] = the sum
         of ap over the classes with positives and their number), device tensors, no synchronisation.  self.ap_flags
         (device int32 [1]) holds the call's flag word: bit 0 a non-finite score, bit 1 a label other than 0 / 1."""
-        s, y = self._f32_rows(scores), self._f32_rows(labels)
-        if s.shape != y.shape:
-            raise ValueError(f"Found input variables with inconsistent shapes: {tuple(y.shape)}, {tuple(s.shape)}")
-        n, c = s.shape
+        s, y, ld_s, ld_y, n, c = self._score_label_rows(scores, labels)
         ap = self.empty((c,), torch.float64)
         n_pos = self.empty((c,), torch.int64)
         pair = self.empty((2,), torch.float64)
         self.ap_flags = flags = self.empty((1,), torch.int32)
-        ld_s = s.stride(0) if n > 1 else c
-        ld_y = y.stride(0) if n > 1 else c
         with torch.cuda.device(self.device):
             _lib.check(self.lib.at_average_precision_f32(self.ctx.handle, _ptr(s), ld_s, _ptr(y), ld_y, n, c, _ptr(ap),
                                                          _ptr(n_pos), _ptr(pair), _ptr(flags), self._stream()))
         return ap, n_pos, pair
+
+    def _score_label_rows(self, scores, labels):
+        """(s, y, ld_s, ld_y, n, c) of a scores / labels pair as the metric entries take them (average_precision's rule)."""
+        s, y = self._f32_rows(scores), self._f32_rows(labels)
+        if s.shape != y.shape:
+            raise ValueError(f"Found input variables with inconsistent shapes: {tuple(y.shape)}, {tuple(s.shape)}")
+        n, c = s.shape
+        return s, y, (s.stride(0) if n > 1 else c), (y.stride(0) if n > 1 else c), n, c
+
+    def ranking_metrics(self, scores, labels, want_ap=True):
+        """Exact per-class ROC AUC and, with want_ap, average precision from one sort per class chunk
+        (at_ranking_metrics_f32): scores, labels as for average_precision -> dict of device tensors, no synchronisation:
+        auc float64 [c] (NaN without a positive or without a negative), two_u int64 [c] (auc = two_u / (2 P N)), n_pos
+        int64 [c], mauc float64 [2] (the sum of the defined auc and their number), and ap float64 [c], map float64 [2]
+        (average_precision's bits) or None.  self.ap_flags as for average_precision."""
+        s, y, ld_s, ld_y, n, c = self._score_label_rows(scores, labels)
+        out = {"auc": self.empty((c,), torch.float64), "two_u": self.empty((c,), torch.int64),
+               "n_pos": self.empty((c,), torch.int64), "mauc": self.empty((2,), torch.float64),
+               "ap": self.empty((c,), torch.float64) if want_ap else None,
+               "map": self.empty((2,), torch.float64) if want_ap else None}
+        self.ap_flags = flags = self.empty((1,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_ranking_metrics_f32(
+                self.ctx.handle, _ptr(s), ld_s, _ptr(y), ld_y, n, c, _ptr(out["ap"]) if want_ap else None,
+                _ptr(out["map"]) if want_ap else None, _ptr(out["auc"]), _ptr(out["two_u"]), _ptr(out["n_pos"]),
+                _ptr(out["mauc"]), _ptr(flags), self._stream()))
+        return out
+
+    def threshold_counts(self, scores, labels, threshold):
+        """Per-class counts of predicted = scores > threshold (strict, in float32) against the labels
+        (at_threshold_counts_f32): -> device int64 [c, 3] = tp, fp, fn; no synchronisation.  self.tc_flags (device int32
+        [1]) holds the call's flag word, bits as for average_precision."""
+        s, y, ld_s, ld_y, n, c = self._score_label_rows(scores, labels)
+        counts = self.empty((c, 3), torch.int64)
+        self.tc_flags = flags = self.empty((1,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_threshold_counts_f32(self.ctx.handle, _ptr(s), ld_s, _ptr(y), ld_y, n, c,
+                                                        float(threshold), _ptr(counts), _ptr(flags), self._stream()))
+        return counts
 
 
 _default: dict = {}

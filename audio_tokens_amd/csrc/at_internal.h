@@ -85,7 +85,7 @@ enum at_ws_slot {
     WS_RAGGED_TAPS1,
     WS_RAGGED_TAPS2,
     WS_RAGGED_TAPS3,
-    WS_AVG_PRECISION,  // at_average_precision_f32: the two key buffers of a class chunk, tile records, tile partial sums
+    WS_AVG_PRECISION,  // at_average_precision_f32 / at_ranking_metrics_f32: the two key buffers of a class chunk, tile records, tile partial sums
     WS_AVG_PRECISION_TMP,   // its rocprim temp storage
     WS_NSLOTS
 };
@@ -196,7 +196,7 @@ struct at_ctx {
     hipEvent_t knn_ev;        // behind the last at_knn_f32 (WS_KNN_IMG / WS_KNN are per context)
     hipStream_t knn_stream;
     int knn_used;
-    hipEvent_t ap_ev;         // behind the last at_average_precision_f32 (WS_AVG_PRECISION / _TMP are per context)
+    hipEvent_t ap_ev;         // behind the last at_average_precision_f32 / at_ranking_metrics_f32 (WS_AVG_PRECISION / _TMP are per context)
     hipStream_t ap_stream;
     int ap_used;
 };

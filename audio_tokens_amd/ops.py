@@ -12,6 +12,8 @@
         (processors/cluster_creator.py:115-117)
     sklearn.metrics.average_precision_score (per class)   ->  average_precision, mean_average_precision
         (utils/metrics_calculator.py:8-33; the class itself: audio_tokens_amd.utils.MetricsCalculator)
+    sklearn.metrics.f1_score / hamming_loss / roc_auc_score ->  f1_score, hamming_loss, roc_auc, mean_roc_auc,
+        (utils/metrics_calculator.py:13-21)                     roc_auc_score, d_prime, classification_metrics
     torchaudio.load (of a .flac file)                     ->  load_flac, load_flac_batch
         (processors/spectrogram_generator.py:99)
     get_spectrogram + get_sequence                        ->  AudioTokenizer
@@ -27,7 +29,9 @@ rows and the per-cluster partial sums/counts are exchanged once per iteration.
 from __future__ import annotations
 
 import collections
+import math
 import os
+import statistics
 import sys
 import time
 from collections import OrderedDict
@@ -38,8 +42,9 @@ import torch
 from .backend import default_backend
 
 __all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "normalize_rows", "silhouette_samples",
-           "silhouette_score", "average_precision", "mean_average_precision", "load_flac", "load_flac_batch",
-           "AudioTokenizer"]
+           "silhouette_score", "average_precision", "mean_average_precision", "roc_auc", "mean_roc_auc",
+           "roc_auc_score", "d_prime", "f1_score", "hamming_loss", "classification_metrics", "load_flac",
+           "load_flac_batch", "AudioTokenizer"]
 
 
 def _is_host(x) -> bool:
@@ -839,15 +844,19 @@ def silhouette_score(X, labels, *, sample_size=None, random_state=None, backend=
     return float(total.item()) / s.numel()
 
 
-def _average_precision_checked(labels, scores, be):
-    """be.average_precision and the one host read behind it: (ap, n_pos) device tensors, map_pair as two floats."""
-    ap, n_pos, pair = be.average_precision(scores, labels)
-    tail = torch.cat([pair, be.ap_flags.double()]).cpu()        # the only synchronisation
-    flags = int(tail[2])
+def _raise_for_flags(flags):
+    """The flag word of the metric kernels (bit 0 a non-finite score, bit 1 a label other than 0 / 1) as ValueError."""
     if flags & 1:
         raise ValueError("Input y_score contains NaN or infinity.")
     if flags & 2:
         raise ValueError("Labels must be 0 or 1 in every class (multilabel-indicator format): found another value.")
+
+
+def _average_precision_checked(labels, scores, be):
+    """be.average_precision and the one host read behind it: (ap, n_pos) device tensors, map_pair as two floats."""
+    ap, n_pos, pair = be.average_precision(scores, labels)
+    tail = torch.cat([pair, be.ap_flags.double()]).cpu()        # the only synchronisation
+    _raise_for_flags(int(tail[2]))
     return ap, n_pos, float(tail[0]), float(tail[1])
 
 
@@ -871,3 +880,111 @@ def mean_average_precision(labels, scores, backend=None):
     be = backend or default_backend()
     _, _, total, count = _average_precision_checked(labels, scores, be)
     return total / count if count > 0 else 0.0
+
+
+def _roc_auc_checked(labels, scores, be):
+    """be.ranking_metrics without the average precision and the one host read behind it: auc as a device tensor, the
+    mAUC pair as two floats."""
+    out = be.ranking_metrics(scores, labels, want_ap=False)
+    tail = torch.cat([out["mauc"], be.ap_flags.double()]).cpu()  # the only synchronisation
+    _raise_for_flags(int(tail[2]))
+    return out["auc"], float(tail[0]), float(tail[1])
+
+
+def roc_auc(labels, scores, backend=None):
+    """sklearn.metrics.roc_auc_score(labels[:, j], scores[:, j]) for every class j on the device, in exact arithmetic
+    (at_ranking_metrics_f32): numpy float64 [c], NaN for the classes without a positive or without a negative (where
+    sklearn raises).  Inputs and errors as for average_precision."""
+    be = backend or default_backend()
+    auc, _, _ = _roc_auc_checked(labels, scores, be)
+    return be.to_host(auc)
+
+
+def mean_roc_auc(labels, scores, backend=None):
+    """mAUC, the AudioSet convention and the counterpart of mean_average_precision's rule: the mean of the per-class ROC
+    AUC over the classes with both a positive and a negative, 0.0 when there is none; a Python float."""
+    be = backend or default_backend()
+    _, total, count = _roc_auc_checked(labels, scores, be)
+    return total / count if count > 0 else 0.0
+
+
+def roc_auc_score(y_true, y_score, backend=None):
+    """sklearn.metrics.roc_auc_score for one binary problem: y_true, y_score 1-D; raises sklearn's ValueError when only
+    one class is present."""
+    be = backend or default_backend()
+    y, s = (torch.as_tensor(a) if not isinstance(a, np.ndarray) else torch.from_numpy(np.ascontiguousarray(a))
+            for a in (y_true, y_score))
+    if y.dim() != 1 or s.dim() != 1:
+        raise ValueError(f"roc_auc_score takes 1-D input: got {tuple(y.shape)}, {tuple(s.shape)}")
+    _, total, count = _roc_auc_checked(y.reshape(-1, 1), s.reshape(-1, 1), be)
+    if count == 0:
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    return total
+
+
+def d_prime(auc):
+    """The sensitivity index AudioSet results carry beside mAP and mAUC: sqrt(2) * Phi^-1(auc), on the host from the
+    standard library; +inf / -inf at 1 / 0, NaN for NaN."""
+    auc = float(auc)
+    if math.isnan(auc):
+        return float("nan")
+    if auc <= 0.0 or auc >= 1.0:
+        return math.copysign(float("inf"), auc - 0.5)
+    return math.sqrt(2.0) * statistics.NormalDist().inv_cdf(auc)
+
+
+def _f1_and_hamming(counts, n):
+    """counts: [c][3] Python ints (tp, fp, fn) -> (per-class F1 list, micro, macro, Hamming loss), sklearn's multilabel
+    rules with zero_division=0.  Every ratio is one correctly rounded fp64 division of exact integers; the macro mean is
+    the correctly rounded sum of the per-class ratios over c."""
+    per_class = [2 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else 0.0 for tp, fp, fn in counts]
+    tp, fp, fn = (sum(col) for col in zip(*counts))
+    micro = 2 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else 0.0
+    return per_class, micro, math.fsum(per_class) / len(counts), (fp + fn) / (n * len(counts))
+
+
+def _threshold_counts_checked(labels, scores, threshold, be):
+    """be.threshold_counts and the one host read behind it: ([c][3] Python ints, n)."""
+    counts = be.threshold_counts(scores, labels, threshold)
+    host = torch.cat([counts.reshape(-1), be.tc_flags.to(torch.int64)]).cpu().tolist()   # the only synchronisation
+    _raise_for_flags(host[-1])
+    return [host[i:i + 3] for i in range(0, len(host) - 1, 3)], len(labels)
+
+
+def f1_score(labels, scores, threshold, average="macro", backend=None):
+    """sklearn.metrics.f1_score(labels, scores > threshold, average=average, zero_division=0) for multilabel input, the
+    counting on the device (at_threshold_counts_f32; the comparison is numpy's: strict, in float32).  "macro": the mean
+    over all c classes, a class without positives and predictions counting 0; "micro": from the summed counts; None:
+    numpy float64 [c].  Unlike sklearn's thresholding, which would quietly take NaN as not predicted, non-finite scores
+    raise ValueError, as do labels other than 0 and 1."""
+    if average not in ("macro", "micro", None):
+        raise ValueError(f"average has to be 'macro', 'micro' or None: got {average!r}")
+    counts, n = _threshold_counts_checked(labels, scores, threshold, backend or default_backend())
+    per_class, micro, macro, _ = _f1_and_hamming(counts, n)
+    return np.asarray(per_class, np.float64) if average is None else micro if average == "micro" else macro
+
+
+def hamming_loss(labels, scores, threshold, backend=None):
+    """sklearn.metrics.hamming_loss(labels, scores > threshold) for multilabel input: (fp + fn) / (n c).  Counting and
+    errors as for f1_score."""
+    counts, n = _threshold_counts_checked(labels, scores, threshold, backend or default_backend())
+    return _f1_and_hamming(counts, n)[3]
+
+
+def classification_metrics(labels, scores, threshold=0.2, backend=None):
+    """What the reference's trainer logs after an epoch (utils/metrics_calculator.py:8-33, the threshold metrics it
+    comments out included) and the AudioSet triple: {"mAP", "mAUC", "d_prime", "f1_score_micro", "f1_score_macro",
+    "hamming_loss"} as Python floats.  One ranking_metrics call (one sort per class chunk), one threshold_counts call
+    and one device-to-host read; d_prime = d_prime(mAUC)."""
+    be = backend or default_backend()
+    rank = be.ranking_metrics(scores, labels)
+    counts = be.threshold_counts(scores, labels, threshold)
+    host = torch.cat([counts.reshape(-1), rank["map"].view(torch.int64), rank["mauc"].view(torch.int64),
+                      be.ap_flags.to(torch.int64), be.tc_flags.to(torch.int64)]).cpu()   # the only synchronisation
+    _raise_for_flags(int(host[-1]) | int(host[-2]))
+    map_sum, map_count, auc_sum, auc_count = host[-6:-2].view(torch.float64).tolist()
+    flat = host[:-6].tolist()
+    _, micro, macro, hamming = _f1_and_hamming([flat[i:i + 3] for i in range(0, len(flat), 3)], len(labels))
+    mauc = auc_sum / auc_count if auc_count > 0 else 0.0
+    return {"mAP": map_sum / map_count if map_count > 0 else 0.0, "mAUC": mauc, "d_prime": d_prime(mauc),
+            "f1_score_micro": micro, "f1_score_macro": macro, "hamming_loss": hamming}

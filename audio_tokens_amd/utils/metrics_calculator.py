@@ -1,10 +1,11 @@
 """The reference's utils/metrics_calculator.py on the device: the mean average precision the trainer reports after
-every epoch and selects its best model by (processors/model_trainer.py:96, _save_if_best_model)."""
+every epoch and selects its best model by (processors/model_trainer.py:96, _save_if_best_model), and beside it the
+threshold metrics that file comments out and the ROC AUC / d' AudioSet results are reported with."""
 import numpy as np
 import torch
 
 from ..backend import default_backend
-from ..ops import mean_average_precision
+from ..ops import classification_metrics, mean_average_precision
 
 
 class MetricsCalculator:
@@ -14,6 +15,13 @@ class MetricsCalculator:
         tensors the trainer keeps its sigmoid outputs where they are and drops the .cpu().numpy().  The batches (a short
         last one included) are concatenated on the device.  -> {"mAP": float}"""
         return {"mAP": MetricsCalculator.calculate_mAP(_concat(labels), _concat(predictions))}
+
+    @staticmethod
+    def compute_all_metrics(predictions, labels, prediction_threshold=0.2):
+        """The same batch lists as compute_metrics -> {"mAP", "mAUC", "d_prime", "f1_score_micro", "f1_score_macro",
+        "hamming_loss"} (ops.classification_metrics: one sort per class chunk and one host read for all six;
+        prediction_threshold: AudioTokensConfig.prediction_threshold, applied as predictions > threshold)."""
+        return classification_metrics(_concat(labels), _concat(predictions), threshold=prediction_threshold)
 
     @staticmethod
     def calculate_mAP(labels, predictions):

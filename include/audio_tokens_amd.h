@@ -453,6 +453,34 @@ int at_silhouette_f32(at_ctx* ctx, const float* x, int d, const int64_t* labels,
 int at_average_precision_f32(at_ctx* ctx, const float* scores, int64_t ld_scores, const float* labels, int64_t ld_labels,
                              int64_t n, int c, double* ap, int64_t* n_pos, double* map, int32_t* flags, void* stream);
 
+/* Exact per-class ROC AUC and its mean, and with ap / map non-NULL the average precision of at_average_precision_f32 (the
+ * same bits for every chunking) from the same sort: mAP, mAUC and d' are the triple AudioSet results are reported in.
+ * Inputs, strides, limits, flags, chunking and workspace are at_average_precision_f32's (the two entries share the
+ * context's workspace: a call on another stream than the previous call of either waits for it).  Per class, with the
+ * groups g of equal scores in descending order (-0.0 == +0.0), tp_g / fp_g the positives / negatives up to the end of g,
+ * P = n_pos[j] and N = n - P:
+ *   two_u[j] = sum_g (fp_g - fp_{g-1}) (tp_g + tp_{g-1})       an exact integer, <= 2 P N < 2^61
+ *   auc[j]   = (double)two_u[j] / (double)(2 P N)              NaN when P == 0 or N == 0
+ * sklearn's roc_auc_score (the trapezoid rule over roc_curve) in exact arithmetic: the correctly rounded quotient of two
+ * correctly rounded integers, so |auc - AUC| <= 3 * 2^-53 (+ O(2^-106)), and sklearn's own value lies within
+ * (G + 10) 2^-53 of auc, G the number of groups.
+ *   ap: DEVICE double [c] or NULL; map: DEVICE double [2] or NULL (both or neither);
+ *   auc: DEVICE double [c]; two_u, n_pos: DEVICE int64 [c];
+ *   mauc: DEVICE double [2]: the rounded sum of auc over the classes with a positive and a negative (ascending class
+ *     order) and their number -- mAUC = mauc[0] / mauc[1]. */
+int at_ranking_metrics_f32(at_ctx* ctx, const float* scores, int64_t ld_scores, const float* labels, int64_t ld_labels,
+                           int64_t n, int c, double* ap, double* map, double* auc, int64_t* two_u, int64_t* n_pos,
+                           double* mauc, int32_t* flags, void* stream);
+
+/* The counts behind the reference's threshold metrics (utils/metrics_calculator.py:13-21: f1_score micro / macro and
+ * hamming_loss on predictions > config.prediction_threshold).  predicted = score > threshold, strict and in fp32 (what
+ * numpy's comparison of a float32 array with a Python float does; -0.0 == +0.0).  scores, labels, strides and flags as
+ * for at_average_precision_f32; 1 <= n < 2^31, 1 <= c <= 32768; threshold finite.
+ *   counts: DEVICE int64 [c][3]: per class tp (predicted, label 1), fp (predicted, label 0), fn (not predicted, label 1).
+ * Integers: deterministic.  No workspace, no host synchronisation. */
+int at_threshold_counts_f32(at_ctx* ctx, const float* scores, int64_t ld_scores, const float* labels, int64_t ld_labels,
+                            int64_t n, int c, float threshold, int64_t* counts, int32_t* flags, void* stream);
+
 /* The k nearest centroids under squared L2 (IndexFlatL2.search(x, k)).  dis(i,j) is at_assign_f32's value bit for bit
  * (the direct form for n < 20); a centroid is listed only if dis(i,j) < +inf (NaN never is).  Row i of the output holds
  * the k smallest (dis, j) in lexicographic order, ascending (ties: lower j first); slots with nothing to list hold
