@@ -604,6 +604,27 @@ class HipBackend(HostHelpers):
                                            self._stream()))
         return ids, dist
 
+    def assign_ip(self, x, c, want_dist=True):
+        """The centroid with the largest inner product of every row (at_assign_ip_f32): x [n, d], c [k, d] -> (ids [n]
+        int64, ip [n] float32 or None); the lowest index on equal products, (-1, -inf) for a row with nothing to list."""
+        x, c = self._f32(x), self._f32(c)
+        assert x.dim() == 2 and c.dim() == 2 and x.shape[1] == c.shape[1]
+        n, d = x.shape
+        ids = self.empty((n,), torch.int64)
+        ip = self.empty((n,), torch.float32) if want_dist else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_assign_ip_f32(self.ctx.handle, _ptr(x), n, d, _ptr(c), c.shape[0], _ptr(ids), _ptr(ip),
+                                                 self._stream()))
+        return ids, ip
+
+    def renorm_rows(self, c) -> torch.Tensor:
+        """faiss' fvec_renorm_L2 on the rows of the contiguous float32 device tensor c [k, d], in place
+        (at_renorm_rows_f32); returns c."""
+        assert c.dim() == 2 and c.dtype == torch.float32 and c.is_contiguous() and c.device == self.device
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_renorm_rows_f32(self.ctx.handle, _ptr(c), c.shape[0], c.shape[1], self._stream()))
+        return c
+
     def assign_hinted(self, x, c, hint_ids, order=None, want_dist=True):
         """Same result as assign(), faster when the hints (the previous assignment) are mostly right.
         hint_ids: int64 [n] per row.  order: what centroid_accum(..., want_order=True) returned for

@@ -87,6 +87,7 @@ enum at_ws_slot {
     WS_RAGGED_TAPS3,
     WS_AVG_PRECISION,  // at_average_precision_f32 / at_ranking_metrics_f32: the two key buffers of a class chunk, tile records, tile partial sums
     WS_AVG_PRECISION_TMP,   // its rocprim temp storage
+    WS_IP_IMG,         // at_assign_ip_f32: chunked centroid image (at_prep_chunked_image)
     WS_NSLOTS
 };
 
@@ -382,7 +383,7 @@ int at_logmel_any(at_ctx* ctx, const Clips& clips, int64_t n_frames, int sample_
                   const float* fb_user_dev, float* out, int frame_major, hipStream_t stream);
 
 // assign.hip: the centroid image of the any-d sweep (tiles of 32 * na rows, features in chunks of 64, |c|^2 of a tile
-// behind its last chunk, +inf for rows >= k); at_chunked_image_tile_floats(d, na) floats per tile.  Used by knn.hip.
+// behind its last chunk, +inf for rows >= k); at_chunked_image_tile_floats(d, na) floats per tile.  Used by knn.hip, ip.hip.
 size_t at_chunked_image_tile_floats(int d, int na);
 int at_prep_chunked_image(at_ctx* ctx, const float* c, int k, int d, int na, float* img, hipStream_t stream);
 

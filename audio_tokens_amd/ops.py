@@ -8,6 +8,8 @@
         (processors/cluster_creator.py:42-56)
     faiss.IndexFlatL2                                     ->  IndexFlatL2
         (processors/spec_tokenizer.py:123-127, 77)
+    faiss.IndexFlatIP                                     ->  IndexFlatIP
+        (not used by the reference: the index of Kmeans(spherical=True))
     sklearn.metrics.silhouette_score                      ->  silhouette_score, silhouette_samples
         (processors/cluster_creator.py:115-117)
     sklearn.metrics.average_precision_score (per class)   ->  average_precision, mean_average_precision
@@ -41,7 +43,7 @@ import torch
 
 from .backend import default_backend
 
-__all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "normalize_rows", "silhouette_samples",
+__all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "IndexFlatIP", "normalize_rows", "silhouette_samples",
            "silhouette_score", "average_precision", "mean_average_precision", "roc_auc", "mean_roc_auc",
            "roc_auc_score", "d_prime", "f1_score", "hamming_loss", "classification_metrics", "load_flac",
            "load_flac_batch", "AudioTokenizer"]
@@ -268,26 +270,36 @@ class Kmeans:
     """faiss.Kmeans(d, k, niter=, verbose=, gpu=) for the reference's use (cluster_creator.py:42-48).
 
     ClusteringParameters are FAISS's defaults: nredo=1, seed=1234, max_points_per_centroid=256,
-    min_points_per_centroid=39, no spherical / int / frozen centroids.  Each train() call is one
+    min_points_per_centroid=39, no int / frozen centroids.  Each train() call is one
     faiss Clustering::train: subsample to k*256 rows with rand_perm(n, seed), initialise from
     `init_centroids` or from rand_perm(n_sub, seed+1), then niter x {nearest centroid, objective,
     ascending-index centroid sums, 1/count, split_clusters}.
+
+    spherical=True is faiss' spherical k-means: the initial centroids are re-normalised (fvec_renorm_L2), every
+    search is the inner-product search of IndexFlatIP (the objective is the sum of the products and grows), the
+    centroids are re-normalised behind split_clusters in every iteration, and `index` is an IndexFlatIP.  Every
+    iteration is one dense sweep: the pruned, hinted and filtered sweeps are exact for the L2 expression only.  It
+    needs a backend with assign_ip() and renorm_rows() (else NotImplementedError).
 
     distributed=True (and torch.distributed initialised): `x` is this rank's block of the global
     row-concatenation in rank order; the result is identical on every rank.
     """
 
     def __init__(self, d, k, niter=20, verbose=False, gpu=True, seed=1234, max_points_per_centroid=256,
-                 min_points_per_centroid=39, distributed=False, process_group=None, backend=None, **kwargs):
+                 min_points_per_centroid=39, distributed=False, process_group=None, backend=None, spherical=False,
+                 **kwargs):
         unsupported = {kk: v for kk, v in kwargs.items() if kk not in ("nredo",) or v != 1}
         if unsupported:
             raise NotImplementedError(f"Kmeans: unsupported ClusteringParameters {sorted(unsupported)}")
+        self.spherical = bool(spherical)
         self.d, self.k, self.niter, self.verbose = int(d), int(k), int(niter), bool(verbose)
         self.gpu = gpu  # accepted for signature compatibility; this implementation is GPU-only
         self.seed = int(seed)
         self.max_points_per_centroid = int(max_points_per_centroid)
         self.min_points_per_centroid = int(min_points_per_centroid)
         self.backend = backend or default_backend()
+        if self.spherical and not (hasattr(self.backend, "assign_ip") and hasattr(self.backend, "renorm_rows")):
+            raise NotImplementedError("Kmeans: spherical=True needs a backend with assign_ip() and renorm_rows()")
         self._dist_enabled, self._group = distributed, process_group
         self.centroids_device = None   # [k, d] device tensor after train(); `.centroids` is its numpy copy (lazy)
         self._centroids_host = None
@@ -367,6 +379,9 @@ class Kmeans:
             assert tuple(cent.shape) == (k, d), f"init_centroids must be [{k}, {d}]"
         else:
             cent = rows_at(be.rand_perm_prefix(ns, self.seed + 1, k))
+        spherical = self.spherical
+        if spherical:
+            cent = be.renorm_rows(cent)
 
         # ---- Lloyd iterations -------------------------------------------------------------
         # Nothing below waits for the device: empty clusters are repaired by a device kernel (same draws, same
@@ -393,7 +408,7 @@ class Kmeans:
         # Iterations after the first reuse the previous assignment as a guess.  With d = 64/128 the
         # sweep is also pruned (exact: see csrc/prune.hip); the spatial grouping of the centroids it
         # relies on is computed once per train() -- it only affects how much gets skipped.
-        prune = (self.prune and hasattr(be, "assign_pruned") and d in (64, 128) and k >= 1024
+        prune = (self.prune and not spherical and hasattr(be, "assign_pruned") and d in (64, 128) and k >= 1024
                  and (k + 31) // 32 <= 512 and xs.shape[0] >= 4096)
         ids = dis = order = vorder = None
         # With few rows per cluster on this rank (sharded runs) a cluster fills a tile or two and sorting its
@@ -469,6 +484,8 @@ class Kmeans:
             tp = time.perf_counter()
             if prune:
                 ids, dis = pruned_assign(it)
+            elif spherical:   # one dense inner-product sweep per iteration; `dis` holds the products
+                ids, dis = be.assign_ip(xs, cent)
             elif ids is None:
                 ids, dis = be.assign(xs, cent)
             else:  # same answer, guided by the previous assignment and its member-list order
@@ -519,6 +536,8 @@ class Kmeans:
             else:
                 be.lloyd_stats(hassign, parts, k, d, stats_dev[it], objs=objs)
                 be.split_clusters_device(hassign, cent, ns, nsplit_dev[it:it + 1])
+            if spherical:
+                cent = be.renorm_rows(cent)
             tp = lap("exchange+finalize+split", tp)
             if prune and timed_events:
                 paced.append(be.record_event_timed())
@@ -597,7 +616,7 @@ class Kmeans:
     def _finish(self, cent, sync=True):
         self.centroids_device = cent
         self._centroids_host = None
-        self.index = IndexFlatL2(self.d, backend=self.backend)
+        self.index = (IndexFlatIP if self.spherical else IndexFlatL2)(self.d, backend=self.backend)
         self.index.add(cent)
         be = self.backend
         if getattr(self, "_grouping_of_result", None) is not None and hasattr(be, "remember_grouping"):
@@ -711,6 +730,57 @@ class IndexFlatL2:
             I = torch.full((x.shape[0], k), -1, dtype=torch.int64, device=be.device)
         else:
             I, D = be.knn(x, self._c, k)
+        return (be.to_host(D), be.to_host(I)) if host else (D, I)
+
+
+class IndexFlatIP:
+    """faiss.IndexFlatIP(d) with add / search(x, 1) / reset / ntotal: the index of Kmeans(spherical=True).
+
+    search(x, 1) returns (D, I), [n, 1] float32 / int64: numpy for host input, device tensors (on the caller's current
+    stream) for device input.  I[i] is the lowest j with the largest inner product among the centroids whose product
+    is > -inf (a NaN product is never listed, +inf is), D[i] that product, exactly at_assign_ip_f32's value.  Rows with
+    nothing to list (NaN rows, an empty index) hold I = -1, D = -inf.  Deviation from faiss: its heap starts from
+    -FLT_MAX rather than -inf, so its empty slots would read D = -FLT_MAX.  k < 1 raises RuntimeError, as faiss does;
+    k > 1 raises NotImplementedError: the top k by inner product is csrc/knn.hip's per-lane list with the key order
+    reversed, a follow-up to this class."""
+
+    def __init__(self, d, backend=None):
+        self.d = int(d)
+        self.backend = backend or default_backend()
+        self._c = None
+
+    @property
+    def ntotal(self) -> int:
+        return 0 if self._c is None else int(self._c.shape[0])
+
+    def reset(self) -> None:
+        self._c = None
+
+    def add(self, c) -> None:
+        c = self.backend._f32(c)
+        assert c.dim() == 2 and c.shape[1] == self.d, f"expected [n, {self.d}]"
+        self._c = c.clone() if self._c is None else torch.cat([self._c, c], 0)
+
+    def assign(self, x, want_dist=True):
+        """Device tensors in, (ids [n] int64, ip [n] float32 or None) out: the search itself."""
+        return self.backend.assign_ip(x, self._c, want_dist=want_dist)
+
+    def search(self, x, k=1):
+        if k < 1:
+            raise RuntimeError(f"IndexFlatIP.search: k must be at least 1, got {k}")
+        if k != 1:
+            raise NotImplementedError("IndexFlatIP.search: k > 1 (the top k by inner product: knn.hip's list with the "
+                                      "key order reversed) is not implemented")
+        host = _is_host(x)
+        be = self.backend
+        x = be._f32(x)
+        assert x.dim() == 2 and x.shape[1] == self.d, f"expected [n, {self.d}]"
+        if self._c is None:
+            D = torch.full((x.shape[0], 1), float("-inf"), device=be.device)
+            I = torch.full((x.shape[0], 1), -1, dtype=torch.int64, device=be.device)
+        else:
+            ids, ip = self.assign(x)
+            D, I = ip.unsqueeze(1), ids.unsqueeze(1)
         return (be.to_host(D), be.to_host(I)) if host else (D, I)
 
 

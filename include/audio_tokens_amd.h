@@ -17,6 +17,7 @@
  *   faiss.IndexFlatL2(d).add(c); .search(x, 1)                             at_assign_f32
  *       processors/spec_tokenizer.py:77, 123-127 (and inside faiss.Kmeans.train)
  *   faiss.IndexFlatL2(d).search(x, k), k >= 2 (not used by the reference)  at_knn_f32
+ *   faiss.IndexFlatIP(d).search(x, 1), Kmeans(spherical=True) (likewise)   at_assign_ip_f32, at_renorm_rows_f32
  *   faiss.Kmeans(d, k, niter).train(x, init_centroids)                     at_rand_perm_mt19937,
  *       processors/cluster_creator.py:42-56                                at_gather_rows_f32,
  *                                                                          at_assign_f32, at_assign_hinted_f32,
@@ -493,6 +494,25 @@ int at_threshold_counts_f32(at_ctx* ctx, const float* scores, int64_t ld_scores,
  * sort per row.  A call on another stream than the context's previous at_knn_f32 waits for that call. */
 int at_knn_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k_c, int k, int64_t* ids,
                float* dist_or_null, void* stream);
+
+/* The centroid with the largest inner product (IndexFlatIP.search(x, 1); the search of spherical k-means).
+ *   ip(i,j) = fmaf chain over the feature index, ascending, from +0 (v_mfma_f32_32x32x2_f32): the ip of at_assign_f32,
+ *   at every n (faiss's small-batch form is the same sum).  Centroid j is listed for row i iff ip(i,j) > -inf: a NaN
+ *   product never is, +inf is.  ids[i] = the lowest j among the listed centroids with the largest ip(i,j); ip[i] = that
+ *   product with its own bits.  Rows with nothing to list (NaN rows) get ids = -1, ip = -inf (faiss's heap would leave
+ *   -FLT_MAX there).
+ *   x: [n][d] fp32; c: [k][d] fp32, 1 <= k <= 2^24; ids: int64 [n]; ip_or_null: float [n].  n == 0 is a no-op.
+ * d % 4 == 0 on 16-byte aligned rows: one dense MFMA sweep (x in registers at d = 64 and 128, re-read per 64-feature
+ * chunk otherwise); everything else: the same chain in scalar code.  Like at_assign_f32 the call keeps its centroid
+ * image in the context: calls of one context are ordered by their streams. */
+int at_assign_ip_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, int64_t* ids,
+                     float* ip_or_null, void* stream);
+
+/* faiss fvec_renorm_L2 on every row of c [k][d], in place (spherical k-means: the centroids after every update).
+ *   nr = fmaf chain of c[f] * c[f], ascending, from +0.  nr > 0: inv = 1.0f / sqrtf(nr), both correctly rounded, and
+ *   c[f] = c[f] * inv, one rounding each (faiss divides in double and narrows: the same value).  Otherwise (a zero row, a
+ *   row that holds a NaN) the row is left untouched.  An nr that overflows gives inv = 0.  One launch. */
+int at_renorm_rows_f32(at_ctx* ctx, float* c, int64_t k, int d, void* stream);
 
 /* ---- FLAC: torchaudio.load(path) for the reference's .flac files (processors/spectrogram_generator.py:99) --------
  * Native FLAC streams of 1-8 channels and 4-24 bits per sample.  The host finds the frames, the device decodes them:
