@@ -625,6 +625,41 @@ class HipBackend(HostHelpers):
             _lib.check(self.lib.at_renorm_rows_f32(self.ctx.handle, _ptr(c), c.shape[0], c.shape[1], self._stream()))
         return c
 
+    def pq_encode(self, x, codebooks, want_dist=False):
+        """Product-quantiser codes (at_pq_encode_f32): x [n, d], codebooks [M, ksub, d / M] (made float32, contiguous,
+        on the device; 1 <= ksub <= 256) -> (codes [n, M] uint8, dist [n, M] float32 or None, bad int32 [1]).
+        codes[i, m] is assign()'s answer for the contiguous slice m of x against codebooks[m]; a sub-vector with no
+        distance below +inf gets code 0, distance +inf, and sets bad[0].  Nothing is read back."""
+        x, cb = self._f32(x), self._f32(codebooks)
+        assert x.dim() == 2 and cb.dim() == 3, "pq_encode: x must be [n, d] and codebooks [M, ksub, dsub]"
+        n, d = x.shape
+        M, ksub, dsub = cb.shape
+        if M * dsub != d:
+            raise ValueError(f"pq_encode: codebooks {tuple(cb.shape)} do not cut rows of {d} features")
+        codes = self.empty((n, M), torch.uint8)
+        dist = self.empty((n, M), torch.float32) if want_dist else None
+        bad = self.zeros((1,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_pq_encode_f32(self.ctx.handle, _ptr(x), n, d, M, ksub, _ptr(cb), _ptr(codes),
+                                                 _ptr(dist), _ptr(bad), self._stream()))
+        return codes, dist, bad
+
+    def pq_decode(self, codes, codebooks):
+        """codes [n, M] uint8, codebooks [M, ksub, dsub] -> float32 [n, M * dsub]: row codes[i, m] of codebook m, copied
+        (at_pq_decode_f32)."""
+        cb = self._f32(codebooks)
+        if isinstance(codes, np.ndarray):
+            codes = torch.from_numpy(np.ascontiguousarray(codes))
+        assert codes.dtype == torch.uint8 and codes.dim() == 2 and cb.dim() == 3 and codes.shape[1] == cb.shape[0]
+        codes = codes.to(self.device).contiguous()
+        n, M = codes.shape
+        ksub, dsub = cb.shape[1], cb.shape[2]
+        out = self.empty((n, M * dsub))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_pq_decode_f32(self.ctx.handle, _ptr(codes), n, M * dsub, M, ksub, _ptr(cb), _ptr(out),
+                                                 self._stream()))
+        return out
+
     def assign_hinted(self, x, c, hint_ids, order=None, want_dist=True):
         """Same result as assign(), faster when the hints (the previous assignment) are mostly right.
         hint_ids: int64 [n] per row.  order: what centroid_accum(..., want_order=True) returned for

@@ -88,6 +88,7 @@ enum at_ws_slot {
     WS_AVG_PRECISION,  // at_average_precision_f32 / at_ranking_metrics_f32: the two key buffers of a class chunk, tile records, tile partial sums
     WS_AVG_PRECISION_TMP,   // its rocprim temp storage
     WS_IP_IMG,         // at_assign_ip_f32: chunked centroid image (at_prep_chunked_image)
+    WS_PQ_IMG,         // at_pq_encode_f32: MFMA-operand image of the M codebooks + their |c|^2 (pq.hip)
     WS_NSLOTS
 };
 
@@ -200,6 +201,9 @@ struct at_ctx {
     hipEvent_t ap_ev;         // behind the last at_average_precision_f32 / at_ranking_metrics_f32 (WS_AVG_PRECISION / _TMP are per context)
     hipStream_t ap_stream;
     int ap_used;
+    hipEvent_t pq_ev;         // behind the last fused at_pq_encode_f32 (WS_PQ_IMG is per context)
+    hipStream_t pq_stream;
+    int pq_used;
 };
 
 // makes launches of `func` with `bytes` of dynamic LDS legal on the context's device (at most one runtime call per

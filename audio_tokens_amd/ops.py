@@ -46,7 +46,7 @@ from .backend import default_backend
 __all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "IndexFlatIP", "normalize_rows", "silhouette_samples",
            "silhouette_score", "average_precision", "mean_average_precision", "roc_auc", "mean_roc_auc",
            "roc_auc_score", "d_prime", "f1_score", "hamming_loss", "classification_metrics", "load_flac",
-           "load_flac_batch", "AudioTokenizer"]
+           "load_flac_batch", "AudioTokenizer", "ProductQuantizer"]
 
 
 def _is_host(x) -> bool:
@@ -782,6 +782,123 @@ class IndexFlatIP:
             ids, ip = self.assign(x)
             D, I = ip.unsqueeze(1), ids.unsqueeze(1)
         return (be.to_host(D), be.to_host(I)) if host else (D, I)
+
+
+class ProductQuantizer:
+    """faiss.ProductQuantizer(d, M, nbits=8) with train / compute_codes / decode: M codebooks of ksub = 256 words, one per
+    sub-vector of dsub = d // M features (M tokens per frame; the reference does not call it).
+
+    train(x): for m = 0 .. M-1 in order, codebook m is bit for bit the `centroids` of Kmeans(dsub, 256, niter=niter,
+    seed=seed, max_points_per_centroid=..., backend=backend).train(xm), xm a contiguous copy of x[:, m*dsub:(m+1)*dsub]:
+    faiss's default training mode, one Clustering per sub-space over an IndexFlatL2(dsub).  Every sub-space uses the same
+    seed and so the same subsample permutation.  Kmeans's errors and its small-training-set warning pass through.
+
+    compute_codes(x) -> uint8 [n, M] (numpy for host input, a device tensor on the caller's current stream for device
+    input): codes[i, m] is IndexFlatL2(dsub) holding codebook m asked .search(xm, 1), at_assign_f32's contract exactly (the
+    direct form when the call has n < 20 rows).  A sub-vector with no distance below +inf (a NaN or Inf in it, or
+    overflow) gets code 0; the call then raises RuntimeError in faiss's words, unless check_finite=False, which returns
+    the codes and skips the one host read.  return_distances=True also returns the winning distances, float32 [n, M]
+    (+inf for such a sub-vector).  decode(codes) -> float32 [n, d], the codebook rows copied.
+
+    A backend with pq_encode() / pq_decode() (HipBackend: csrc/pq.hip) does each call in one launch; any other backend
+    composes one assign() per sub-space on the contiguous slice, and decodes by indexing.  nbits != 8 raises
+    NotImplementedError (faiss bit-packs other widths)."""
+
+    def __init__(self, d, M, nbits=8, niter=25, seed=1234, max_points_per_centroid=256, verbose=False, backend=None):
+        d, M, nbits = int(d), int(M), int(nbits)
+        if M < 1 or d < 1 or d % M != 0:
+            raise ValueError(f"ProductQuantizer: the dimension d = {d} must be a multiple of the number of sub-quantisers M = {M}")
+        if nbits != 8:
+            raise NotImplementedError(f"ProductQuantizer: nbits = {nbits} (only 8-bit codes, one byte per sub-space, are implemented)")
+        self.d, self.M, self.nbits = d, M, nbits
+        self.dsub, self.ksub, self.code_size = d // M, 256, M
+        self.niter, self.seed, self.verbose = int(niter), int(seed), bool(verbose)
+        self.max_points_per_centroid = int(max_points_per_centroid)
+        self.backend = backend or default_backend()
+        self.centroids_device = None   # [M, ksub, dsub] device tensor after train() / set_centroids()
+        self._centroids_host = None
+
+    @property
+    def is_trained(self) -> bool:
+        return self.centroids_device is not None
+
+    @property
+    def centroids(self):
+        """numpy [M, ksub, dsub] float32 (None before training)."""
+        if self._centroids_host is None and self.centroids_device is not None:
+            self._centroids_host = self.backend.to_host(self.centroids_device)
+        return self._centroids_host
+
+    def set_centroids(self, c) -> None:
+        """Takes a ready [M, 256, dsub] table (host or device) without training."""
+        c = self.backend._f32(c)
+        want = (self.M, self.ksub, self.dsub)
+        if tuple(c.shape) != want:
+            raise ValueError(f"ProductQuantizer.set_centroids: expected {list(want)}, got {list(c.shape)}")
+        self.centroids_device = c.clone()
+        self._centroids_host = None
+
+    def _rows(self, x, what):
+        x = self.backend._f32(x)
+        assert x.dim() == 2 and x.shape[1] == self.d, f"{what}: expected [n, {self.d}], got {tuple(x.shape)}"
+        return x
+
+    def _require_trained(self, what):
+        if not self.is_trained:
+            raise RuntimeError(f"ProductQuantizer.{what}: the quantiser is not trained (call train() or set_centroids())")
+
+    def train(self, x) -> None:
+        be = self.backend
+        x = self._rows(x, "ProductQuantizer.train")
+        books = []
+        for m in range(self.M):
+            km = Kmeans(self.dsub, self.ksub, niter=self.niter, verbose=self.verbose, seed=self.seed,
+                        max_points_per_centroid=self.max_points_per_centroid, backend=be)
+            km.train(x[:, m * self.dsub:(m + 1) * self.dsub].contiguous())
+            books.append(km.centroids_device)
+        self.centroids_device = torch.stack(books, 0).contiguous()
+        self._centroids_host = None
+
+    def compute_codes(self, x, return_distances=False, check_finite=True):
+        self._require_trained("compute_codes")
+        be = self.backend
+        host = _is_host(x)
+        x = self._rows(x, "ProductQuantizer.compute_codes")
+        cb = self.centroids_device
+        if hasattr(be, "pq_encode"):
+            codes, dist, bad = be.pq_encode(x, cb, want_dist=return_distances)
+        else:
+            ids, dis = [], []
+            for m in range(self.M):
+                i_m, d_m = be.assign(x[:, m * self.dsub:(m + 1) * self.dsub].contiguous(), cb[m], want_dist=return_distances)
+                ids.append(i_m)
+                dis.append(d_m)
+            ids = torch.stack(ids, 1) if ids else torch.zeros((x.shape[0], 0), dtype=torch.int64)
+            bad = (ids < 0).any().reshape(1).to(torch.int32)
+            codes = ids.clamp(min=0).to(torch.uint8)
+            # (the assignment leaves +inf where it lists nothing)
+            dist = torch.stack(dis, 1).contiguous() if return_distances else None
+        if check_finite and x.shape[0] and int(bad.item()):
+            raise RuntimeError("Error: 'std::isfinite(x_in[i])' failed: input contains NaN's or Inf's")
+        if host:
+            codes, dist = be.to_host(codes), (be.to_host(dist) if return_distances else None)
+        return (codes, dist) if return_distances else codes
+
+    def decode(self, codes):
+        self._require_trained("decode")
+        be = self.backend
+        host = _is_host(codes)
+        if isinstance(codes, np.ndarray):
+            codes = torch.from_numpy(np.ascontiguousarray(codes))
+        assert codes.dim() == 2 and codes.shape[1] == self.M and codes.dtype == torch.uint8, \
+            f"ProductQuantizer.decode: expected uint8 [n, {self.M}]"
+        cb = self.centroids_device
+        if hasattr(be, "pq_decode"):
+            out = be.pq_decode(codes, cb)
+        else:
+            idx = codes.to(torch.int64)
+            out = torch.cat([cb[m][idx[:, m]] for m in range(self.M)], 1).contiguous()
+        return be.to_host(out) if host else out
 
 
 class AudioTokenizer:

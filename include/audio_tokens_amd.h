@@ -18,6 +18,7 @@
  *       processors/spec_tokenizer.py:77, 123-127 (and inside faiss.Kmeans.train)
  *   faiss.IndexFlatL2(d).search(x, k), k >= 2 (not used by the reference)  at_knn_f32
  *   faiss.IndexFlatIP(d).search(x, 1), Kmeans(spherical=True) (likewise)   at_assign_ip_f32, at_renorm_rows_f32
+ *   faiss.ProductQuantizer(d, M, 8).compute_codes(x) / .decode(codes) (likewise)  at_pq_encode_f32, at_pq_decode_f32
  *   faiss.Kmeans(d, k, niter).train(x, init_centroids)                     at_rand_perm_mt19937,
  *       processors/cluster_creator.py:42-56                                at_gather_rows_f32,
  *                                                                          at_assign_f32, at_assign_hinted_f32,
@@ -513,6 +514,28 @@ int at_assign_ip_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float*
  *   c[f] = c[f] * inv, one rounding each (faiss divides in double and narrows: the same value).  Otherwise (a zero row, a
  *   row that holds a NaN) the row is left untouched.  An nr that overflows gives inv = 0.  One launch. */
 int at_renorm_rows_f32(at_ctx* ctx, float* c, int64_t k, int d, void* stream);
+
+/* Product quantiser, encoder (faiss ProductQuantizer::compute_codes at nbits = 8).  A row of d features is cut into M
+ * sub-vectors of dsub = d / M features; sub-space m has the codebook codebooks[m] of ksub rows.  codes[i][m] is
+ * at_assign_f32's answer for (sub-vector m of the rows as an [n][dsub] matrix, codebooks[m]), bit for bit: ascending fmaf
+ * chains for |x|^2, |c|^2 and <x, c> over the dsub features, dis = fma(-2, ip, xn + cn), the clamp v < 0 ? 0 : v, the
+ * lowest index on equal distances, and the direct form sum (x-c)^2 when the CALL has n < 20 rows.  A sub-vector with no
+ * distance below +inf (a NaN or Inf in it, or overflow) gets code 0 and distance +inf, and sets *bad.
+ *   x: [n][d] fp32; codebooks: [M][ksub][d/M] fp32; 1 <= ksub <= 256, d % M == 0, n >= 0 (n == 0 is a no-op that
+ *   touches no pointer); codes: uint8 [n][M]; dist_or_null: float [n][M], the winning distances; bad_or_null: DEVICE
+ *   int32, written by every call with n > 0: 0, then 1 if some sub-vector had nothing to list.
+ * ksub == 256, dsub % 4 == 0, 16-byte aligned rows, n >= 20 and d + M <= 160 (all M codebooks and their norms in the
+ * 160 KiB of LDS of a CU): one launch in which every workgroup keeps the whole MFMA-operand image of the codebooks in
+ * LDS and x is read once.  Everything else: one thread per (row, sub-space) with the same chains in scalar code.  The
+ * fused form keeps its image in the context: a call on another stream than the context's previous one waits for it. */
+int at_pq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, int M, int ksub, const float* codebooks,
+                     uint8_t* codes, float* dist_or_null, int32_t* bad_or_null, void* stream);
+
+/* Product quantiser, decoder: out[i][m * dsub + f] = codebooks[m][codes[i][m]][f], copied bits (a code >= ksub, which
+ * no encoder produces, decodes to NaN).  Sizes as for at_pq_encode_f32; out: float [n][d].  16-byte accesses where
+ * dsub % 4 == 0 and codebooks / out are 16-byte aligned, one float per thread otherwise.  No workspace. */
+int at_pq_decode_f32(at_ctx* ctx, const uint8_t* codes, int64_t n, int d, int M, int ksub, const float* codebooks,
+                     float* out, void* stream);
 
 /* ---- FLAC: torchaudio.load(path) for the reference's .flac files (processors/spectrogram_generator.py:99) --------
  * Native FLAC streams of 1-8 channels and 4-24 bits per sample.  The host finds the frames, the device decodes them:
