@@ -660,6 +660,43 @@ class HipBackend(HostHelpers):
                                                  self._stream()))
         return out
 
+    def rq_encode(self, x, codebooks, want_dist=False, want_residual=False):
+        """Greedy residual-quantiser codes (at_rq_encode_f32): x [n, d], codebooks [M, ksub, d] (made float32,
+        contiguous, on the device; 1 <= ksub <= 256) -> (codes [n, M] uint8, dist [n, M] float32 or None, residual
+        [n, d] float32 or None, bad int32 [1]).  Stage m is assign()'s answer for the running residual against
+        codebooks[m], then residual -= codebooks[m][code]; a row with no distance below +inf at a stage gets code 0,
+        distance +inf, and sets bad[0].  Nothing is read back."""
+        x, cb = self._f32(x), self._f32(codebooks)
+        assert x.dim() == 2 and cb.dim() == 3, "rq_encode: x must be [n, d] and codebooks [M, ksub, d]"
+        n, d = x.shape
+        M, ksub, dc = cb.shape
+        if dc != d:
+            raise ValueError(f"rq_encode: codebooks {tuple(cb.shape)} do not hold rows of {d} features")
+        codes = self.empty((n, M), torch.uint8)
+        dist = self.empty((n, M), torch.float32) if want_dist else None
+        residual = self.empty((n, d), torch.float32) if want_residual else None
+        bad = self.zeros((1,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_rq_encode_f32(self.ctx.handle, _ptr(x), n, d, M, ksub, _ptr(cb), _ptr(codes),
+                                                 _ptr(dist), _ptr(residual), _ptr(bad), self._stream()))
+        return codes, dist, residual, bad
+
+    def rq_decode(self, codes, codebooks):
+        """codes [n, M] uint8, codebooks [M, ksub, d] -> float32 [n, d]: row codes[i, 0] of codebook 0, then the rows
+        codes[i, m] of the codebooks m = 1 .. M-1 added in ascending order (at_rq_decode_f32)."""
+        cb = self._f32(codebooks)
+        if isinstance(codes, np.ndarray):
+            codes = torch.from_numpy(np.ascontiguousarray(codes))
+        assert codes.dtype == torch.uint8 and codes.dim() == 2 and cb.dim() == 3 and codes.shape[1] == cb.shape[0]
+        codes = codes.to(self.device).contiguous()
+        n, M = codes.shape
+        ksub, d = cb.shape[1], cb.shape[2]
+        out = self.empty((n, d))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_rq_decode_f32(self.ctx.handle, _ptr(codes), n, d, M, ksub, _ptr(cb), _ptr(out),
+                                                 self._stream()))
+        return out
+
     def assign_hinted(self, x, c, hint_ids, order=None, want_dist=True):
         """Same result as assign(), faster when the hints (the previous assignment) are mostly right.
         hint_ids: int64 [n] per row.  order: what centroid_accum(..., want_order=True) returned for

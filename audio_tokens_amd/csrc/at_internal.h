@@ -89,6 +89,8 @@ enum at_ws_slot {
     WS_AVG_PRECISION_TMP,   // its rocprim temp storage
     WS_IP_IMG,         // at_assign_ip_f32: chunked centroid image (at_prep_chunked_image)
     WS_PQ_IMG,         // at_pq_encode_f32: MFMA-operand image of the M codebooks + their |c|^2 (pq.hip)
+    WS_RQ_IMG,         // at_rq_encode_f32: chunked centroid image of the M stage codebooks (at_prep_chunked_image)
+    WS_RQ_TMP,         // at_rq_encode_f32 general path: the running residual, when the caller takes none
     WS_NSLOTS
 };
 
@@ -204,6 +206,9 @@ struct at_ctx {
     hipEvent_t pq_ev;         // behind the last fused at_pq_encode_f32 (WS_PQ_IMG is per context)
     hipStream_t pq_stream;
     int pq_used;
+    hipEvent_t rq_ev;         // behind the last at_rq_encode_f32 (WS_RQ_IMG / WS_RQ_TMP are per context)
+    hipStream_t rq_stream;
+    int rq_used;
 };
 
 // makes launches of `func` with `bytes` of dynamic LDS legal on the context's device (at most one runtime call per
@@ -387,7 +392,7 @@ int at_logmel_any(at_ctx* ctx, const Clips& clips, int64_t n_frames, int sample_
                   const float* fb_user_dev, float* out, int frame_major, hipStream_t stream);
 
 // assign.hip: the centroid image of the any-d sweep (tiles of 32 * na rows, features in chunks of 64, |c|^2 of a tile
-// behind its last chunk, +inf for rows >= k); at_chunked_image_tile_floats(d, na) floats per tile.  Used by knn.hip, ip.hip.
+// behind its last chunk, +inf for rows >= k); at_chunked_image_tile_floats(d, na) floats per tile.  Used by knn.hip, ip.hip, rq.hip.
 size_t at_chunked_image_tile_floats(int d, int na);
 int at_prep_chunked_image(at_ctx* ctx, const float* c, int k, int d, int na, float* img, hipStream_t stream);
 

@@ -187,6 +187,7 @@ void at_destroy(at_ctx* ctx) {
     if (ctx->sil_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sil_ev));
     if (ctx->knn_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->knn_ev));
     if (ctx->pq_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->pq_ev));
+    if (ctx->rq_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->rq_ev));
     if (ctx->ap_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->ap_ev));
     if (ctx->filter.host_misc) (void)AT_HIP_TOLERATE(hipHostFree(ctx->filter.host_misc));
     at_logmel_tables_clear(&ctx->lm_fb);

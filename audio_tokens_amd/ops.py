@@ -46,7 +46,7 @@ from .backend import default_backend
 __all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "IndexFlatIP", "normalize_rows", "silhouette_samples",
            "silhouette_score", "average_precision", "mean_average_precision", "roc_auc", "mean_roc_auc",
            "roc_auc_score", "d_prime", "f1_score", "hamming_loss", "classification_metrics", "load_flac",
-           "load_flac_batch", "AudioTokenizer", "ProductQuantizer"]
+           "load_flac_batch", "AudioTokenizer", "ProductQuantizer", "ResidualQuantizer"]
 
 
 def _is_host(x) -> bool:
@@ -898,6 +898,152 @@ class ProductQuantizer:
         else:
             idx = codes.to(torch.int64)
             out = torch.cat([cb[m][idx[:, m]] for m in range(self.M)], 1).contiguous()
+        return be.to_host(out) if host else out
+
+
+class ResidualQuantizer:
+    """Greedy residual vector quantiser (RVQ: SoundStream, EnCodec; faiss calls the family ResidualQuantizer): M
+    codebooks of ksub = 256 words of d features.  Stage 0 quantises the frame, stage m what the stages before it left
+    over; M one-byte tokens per frame, coarse to fine, every prefix of a code a valid coarser code.  Beam width 1 and one
+    plain k-means per stage: faiss's own defaults (a beam of 5, progressive-dimension training) are not implemented, and
+    the contract below is the library's own, not verified faiss output.  max_beam_size != 1 and nbits != 8 raise
+    NotImplementedError.
+
+    train(x): r_0 = x; for m = 0 .. M-1 in order, codebook m is bit for bit the `centroids` of Kmeans(d, 256,
+    niter=niter, seed=seed, max_points_per_centroid=..., backend=backend).train(r_m), and r_{m+1} is one encode stage
+    over ALL rows of r_m (not the subsample).  Every stage uses the same seed and so the same subsample permutation;
+    codebook 0 is the plain Kmeans vocabulary.  Kmeans's errors and its small-training-set warning pass through.
+
+    compute_codes(x) -> uint8 [n, M] (numpy for host input, a device tensor on the caller's current stream for device
+    input).  r_0 = x; for m = 0 .. M-1: codes[i, m] is IndexFlatL2(d) holding codebook m asked .search(r_m, 1),
+    at_assign_f32's contract exactly (the direct form when the call has n < 20 rows), then
+    r_{m+1}[i] = r_m[i] - codebook[m, codes[i, m]], one fp32 subtraction per feature.  A row with no distance below +inf
+    at a stage (a NaN or Inf in it, or overflow) gets code 0 and distance +inf there and subtracts word 0; the call then
+    raises RuntimeError in faiss's words, unless check_finite=False, which returns the codes and skips the one host read.
+    return_distances=True also returns the winning distances, float32 [n, M] (column M-1 is the squared reconstruction
+    error in the expansion form), return_residual=True r_M, float32 [n, d]; the tuple is (codes, dist, residual).
+
+    decode(codes) -> float32 [n, d]: codebook[0, codes[:, 0]] copied, then + codebook[m, codes[:, m]] for m = 1 .. M-1 in
+    ascending order, one fp32 addition each.  (decode(codes) + residual is not x bit for bit: fp32 addition does not
+    invert the subtractions.)
+
+    A backend with rq_encode() / rq_decode() (HipBackend: csrc/rq.hip) does each call in the library, all M stages in
+    one launch at d = 64 and 128; any other backend composes one assign() per stage and a torch subtraction, and
+    decodes by indexing and adding."""
+
+    def __init__(self, d, M, nbits=8, niter=25, seed=1234, max_points_per_centroid=256, max_beam_size=1, verbose=False,
+                 backend=None):
+        d, M, nbits, max_beam_size = int(d), int(M), int(nbits), int(max_beam_size)
+        if M < 1 or d < 1:
+            raise ValueError(f"ResidualQuantizer: d = {d} and M = {M} must both be at least 1")
+        if nbits != 8:
+            raise NotImplementedError(f"ResidualQuantizer: nbits = {nbits} (only 8-bit codes, one byte per stage, are implemented)")
+        if max_beam_size != 1:
+            raise NotImplementedError(f"ResidualQuantizer: max_beam_size = {max_beam_size} (only the greedy encoder, a beam "
+                                      "of 1, is implemented)")
+        self.d, self.M, self.nbits, self.max_beam_size = d, M, nbits, max_beam_size
+        self.ksub, self.code_size = 256, M
+        self.niter, self.seed, self.verbose = int(niter), int(seed), bool(verbose)
+        self.max_points_per_centroid = int(max_points_per_centroid)
+        self.backend = backend or default_backend()
+        self.centroids_device = None   # [M, ksub, d] device tensor after train() / set_centroids()
+        self._centroids_host = None
+
+    @property
+    def is_trained(self) -> bool:
+        return self.centroids_device is not None
+
+    @property
+    def centroids(self):
+        """numpy [M, ksub, d] float32 (None before training)."""
+        if self._centroids_host is None and self.centroids_device is not None:
+            self._centroids_host = self.backend.to_host(self.centroids_device)
+        return self._centroids_host
+
+    def set_centroids(self, c) -> None:
+        """Takes a ready [M, 256, d] table (host or device) without training."""
+        c = self.backend._f32(c)
+        want = (self.M, self.ksub, self.d)
+        if tuple(c.shape) != want:
+            raise ValueError(f"ResidualQuantizer.set_centroids: expected {list(want)}, got {list(c.shape)}")
+        self.centroids_device = c.clone()
+        self._centroids_host = None
+
+    def _rows(self, x, what):
+        x = self.backend._f32(x)
+        assert x.dim() == 2 and x.shape[1] == self.d, f"{what}: expected [n, {self.d}], got {tuple(x.shape)}"
+        return x
+
+    def _require_trained(self, what):
+        if not self.is_trained:
+            raise RuntimeError(f"ResidualQuantizer.{what}: the quantiser is not trained (call train() or set_centroids())")
+
+    def _encode(self, x, cb, want_dist, want_residual):
+        """-> (codes, dist or None, residual or None, bad int32 [1]) on the backend's device, nothing read back."""
+        be = self.backend
+        if hasattr(be, "rq_encode"):
+            return be.rq_encode(x, cb, want_dist=want_dist, want_residual=want_residual)
+        r, ids, dis = x, [], []
+        for m in range(cb.shape[0]):
+            i_m, d_m = be.assign(r, cb[m], want_dist=want_dist)
+            ids.append(i_m)
+            if want_dist:
+                dis.append(torch.where(i_m < 0, torch.full_like(d_m, float("inf")), d_m))
+            if want_residual or m + 1 < cb.shape[0]:
+                r = r - cb[m][i_m.clamp(min=0)]
+        ids = torch.stack(ids, 1)
+        bad = (ids < 0).any().reshape(1).to(torch.int32)
+        return (ids.clamp(min=0).to(torch.uint8), torch.stack(dis, 1).contiguous() if want_dist else None,
+                r.contiguous() if want_residual else None, bad)
+
+    def train(self, x) -> None:
+        be = self.backend
+        r = self._rows(x, "ResidualQuantizer.train")
+        books = []
+        for m in range(self.M):
+            km = Kmeans(self.d, self.ksub, niter=self.niter, verbose=self.verbose, seed=self.seed,
+                        max_points_per_centroid=self.max_points_per_centroid, backend=be)
+            km.train(r)
+            books.append(km.centroids_device)
+            if m + 1 < self.M:
+                r = self._encode(r, km.centroids_device.unsqueeze(0), False, True)[2]
+        self.centroids_device = torch.stack(books, 0).contiguous()
+        self._centroids_host = None
+
+    def compute_codes(self, x, return_distances=False, return_residual=False, check_finite=True):
+        self._require_trained("compute_codes")
+        be = self.backend
+        host = _is_host(x)
+        x = self._rows(x, "ResidualQuantizer.compute_codes")
+        if x.shape[0] == 0:
+            codes, bad = be.empty((0, self.M), torch.uint8), None
+            dist = be.empty((0, self.M)) if return_distances else None
+            res = be.empty((0, self.d)) if return_residual else None
+        else:
+            codes, dist, res, bad = self._encode(x, self.centroids_device, return_distances, return_residual)
+        if check_finite and bad is not None and int(bad.item()):
+            raise RuntimeError("Error: 'std::isfinite(x_in[i])' failed: input contains NaN's or Inf's")
+        out = [codes] + ([dist] if return_distances else []) + ([res] if return_residual else [])
+        if host:
+            out = [be.to_host(t) for t in out]
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def decode(self, codes):
+        self._require_trained("decode")
+        be = self.backend
+        host = _is_host(codes)
+        if isinstance(codes, np.ndarray):
+            codes = torch.from_numpy(np.ascontiguousarray(codes))
+        assert codes.dim() == 2 and codes.shape[1] == self.M and codes.dtype == torch.uint8, \
+            f"ResidualQuantizer.decode: expected uint8 [n, {self.M}]"
+        cb = self.centroids_device
+        if hasattr(be, "rq_decode"):
+            out = be.rq_decode(codes, cb)
+        else:
+            idx = codes.to(torch.int64)
+            out = cb[0][idx[:, 0]].clone()
+            for m in range(1, self.M):
+                out = out + cb[m][idx[:, m]]
         return be.to_host(out) if host else out
 
 

@@ -19,6 +19,7 @@
  *   faiss.IndexFlatL2(d).search(x, k), k >= 2 (not used by the reference)  at_knn_f32
  *   faiss.IndexFlatIP(d).search(x, 1), Kmeans(spherical=True) (likewise)   at_assign_ip_f32, at_renorm_rows_f32
  *   faiss.ProductQuantizer(d, M, 8).compute_codes(x) / .decode(codes) (likewise)  at_pq_encode_f32, at_pq_decode_f32
+ *   greedy residual quantiser (RVQ, beam 1; the library's own contract)    at_rq_encode_f32, at_rq_decode_f32
  *   faiss.Kmeans(d, k, niter).train(x, init_centroids)                     at_rand_perm_mt19937,
  *       processors/cluster_creator.py:42-56                                at_gather_rows_f32,
  *                                                                          at_assign_f32, at_assign_hinted_f32,
@@ -535,6 +536,33 @@ int at_pq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, int M, int k
  * no encoder produces, decodes to NaN).  Sizes as for at_pq_encode_f32; out: float [n][d].  16-byte accesses where
  * dsub % 4 == 0 and codebooks / out are 16-byte aligned, one float per thread otherwise.  No workspace. */
 int at_pq_decode_f32(at_ctx* ctx, const uint8_t* codes, int64_t n, int d, int M, int ksub, const float* codebooks,
+                     float* out, void* stream);
+
+/* Residual quantiser (RVQ), greedy encoder: beam width 1, M dependent stages.  r_0 = x; for m = 0 .. M-1 in order,
+ * (codes[i][m], dist[i][m]) is at_assign_f32's answer for the rows r_m against codebooks[m] ([ksub][d]), bit for bit:
+ * ascending fmaf chains for |r|^2, |c|^2 and <r, c> over the d features, dis = fma(-2, ip, rn + cn), the clamp
+ * v < 0 ? 0 : v, the lowest index on equal distances, and the direct form sum (r-c)^2 when the CALL has n < 20 rows.
+ * A row with no distance below +inf at a stage (a NaN or Inf in it, or overflow) gets code 0 and distance +inf there,
+ * and sets *bad.  Then r_{m+1}[i][f] = r_m[i][f] - codebooks[m][codes[i][m]][f], one fp32 subtraction (a flagged row
+ * subtracts row 0 like any other; a NaN stays a NaN).  Column M-1 of dist is the squared reconstruction error in the
+ * expansion form.  The contract is the library's own, not verified faiss output (faiss's ResidualQuantizer defaults
+ * to a beam of 5).
+ *   x: [n][d] fp32; codebooks: [M][ksub][d] fp32; 1 <= ksub <= 256, M >= 1, d >= 1, n >= 0 (n == 0 is a no-op that
+ *   touches no pointer); codes: uint8 [n][M]; dist_or_null: float [n][M]; residual_or_null: float [n][d], r_M, must
+ *   not overlap x; bad_or_null: DEVICE int32, written by every call with n > 0: 0, then 1 if some row had nothing to
+ *   list at some stage.
+ * d = 64 or 128, n >= 20 and 16-byte aligned x, codebooks and residual: one launch for all M stages, the residual in
+ * registers, the codebooks streamed through LDS from a chunked image kept in the context.  Everything else: one launch
+ * of the same chains in scalar code, a workgroup per 8 rows, the residual in the caller's buffer or in the context.  A
+ * call on another stream than the context's previous at_rq_encode_f32 waits for that call. */
+int at_rq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, int M, int ksub, const float* codebooks,
+                     uint8_t* codes, float* dist_or_null, float* residual_or_null, int32_t* bad_or_null, void* stream);
+
+/* Residual quantiser, decoder: out[i] = codebooks[0][codes[i][0]], copied, then out[i] = out[i] + codebooks[m][codes[i][m]]
+ * for m = 1 .. M-1 in ascending order, one fp32 addition each (a code >= ksub, which no encoder produces, makes the
+ * whole row NaN).  Sizes as for at_rq_encode_f32; out: float [n][d].  16-byte accesses where d % 4 == 0 and codebooks /
+ * out are 16-byte aligned, one float per thread otherwise.  No workspace. */
+int at_rq_decode_f32(at_ctx* ctx, const uint8_t* codes, int64_t n, int d, int M, int ksub, const float* codebooks,
                      float* out, void* stream);
 
 /* ---- FLAC: torchaudio.load(path) for the reference's .flac files (processors/spectrogram_generator.py:99) --------
