@@ -5,8 +5,9 @@
 //     norms = np.linalg.norm(vectors, axis=1, keepdims=True);  vectors / (norms + 1e-10)
 // numpy evaluates this in fp32 as sqrt(add.reduce(x*x)) with its pairwise summation (8 running
 // sums over blocks of <= 128, combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), halves split at a
-// multiple of 8 above 128), then one add and one IEEE division per element.  The same order is
-// used here, so the result is bit-identical to numpy's.  HBM-bound: 8d bytes per row.
+// multiple of 8 above 128; a row longer than numpy's buffer of 8192 elements piece by piece, see
+// l2norm_core.h), then one add and one IEEE division per element.  The same order is used here, so
+// the result is bit-identical to numpy's.  HBM-bound: 8d bytes per row.
 //
 // Layout: a workgroup stages R rows in LDS (coalesced reads, row pitch d+1 so a row-per-thread
 // walk is bank-conflict free), R threads reduce one row each, then all threads divide and store

@@ -65,9 +65,25 @@ __device__ inline float pairwise_sumsq_8lanes(const float* a, int n, int j) {
     return r;
 }
 
+// add.reduce(x * x) of a whole row: numpy's reduction hands its inner loop at most bufsize = 8192 elements (numpy's
+// default, np.getbufsize()) at a time, so a longer row is the running sum, from +0, of the pairwise sums of its pieces of
+// 8192.  Up to 8192 that is the one tree (+0 + s == s for a sum of squares), at 16384 the two agree; between the two
+// the plain tree splits the row elsewhere (near n / 2) and differs from numpy in about a third of Gaussian rows.
+constexpr int NUMPY_BUFSIZE = 8192;
+
+__device__ inline float chunked_pairwise_sumsq(const float* a, int n, int stride) {
+#pragma clang fp contract(off)
+    float res = 0.0f;
+    for (int at = 0; at < n; at += NUMPY_BUFSIZE) {
+        const int len = n - at < NUMPY_BUFSIZE ? n - at : NUMPY_BUFSIZE;
+        res = res + pairwise_sumsq(a + (size_t)at * stride, len, stride);
+    }
+    return res;
+}
+
 // ||row|| + 1e-10 as numpy computes it for a float32 row
 __device__ inline float row_denominator(const float* a, int n, int stride) {
-    return __builtin_sqrtf(pairwise_sumsq(a, n, stride)) + 1e-10f;
+    return __builtin_sqrtf(chunked_pairwise_sumsq(a, n, stride)) + 1e-10f;
 }
 
 // x / den, IEEE-rounded

@@ -130,11 +130,19 @@ static float np_pairwise_sumsq(const float* a, int64_t n) {
     }
 }
 
+/* add.reduce over a whole row: numpy's reduction hands the inner loop at most bufsize = 8192 elements (its default) at
+ * a time, so a row longer than that is the running sum, from +0, of the pairwise sums of its pieces of 8192. */
+static float np_reduce_sumsq(const float* a, int64_t n) {
+    float res = 0.f;
+    for (int64_t at = 0; at < n; at += 8192) res += np_pairwise_sumsq(a + at, n - at < 8192 ? n - at : 8192);
+    return res;
+}
+
 void orc_l2norm_rows(const float* x, int64_t n, int d, float* y) {
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n; i++) {
         const float* xi = x + i * (int64_t)d;
-        float nrm = sqrtf(np_pairwise_sumsq(xi, d));
+        float nrm = sqrtf(np_reduce_sumsq(xi, d));
         float den = nrm + 1e-10f; /* float32 array + python float -> float32 */
         float* yi = y + i * (int64_t)d;
         for (int j = 0; j < d; j++) yi[j] = xi[j] / den;

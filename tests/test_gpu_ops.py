@@ -455,7 +455,7 @@ def test_centroid_accum_sort_path_with_more_long_clusters_than_early_slots(be, s
 def test_conv1d_mel_matches_torch(be, n_mels, nk, ks):
     """use_convolution (SURVEY 8f row 3): Conv1d(1, nk, ks, padding=ks//2) along the mel axis by at_conv1d_mel_f32 against
     torch's conv1d on the CPU (tolerance: the two sum the taps in their own order) and, exactly, against the taps added
-    in ascending order in float64 rounded once per fma; layout feature = mel * nk + kernel."""
+    in ascending order, one exact fmaf each; layout feature = mel * nk + kernel."""
     torch.manual_seed(n_mels + nk)
     conv = torch.nn.Conv1d(1, nk, ks, padding=ks // 2)
     x = torch.randn(5000, n_mels) * 20 - 30
@@ -464,13 +464,11 @@ def test_conv1d_mel_matches_torch(be, n_mels, nk, ks):
     got = be.conv1d_mel(x, conv.weight.detach(), conv.bias.detach(), padding=ks // 2).cpu()
     assert got.shape == want.shape
     assert torch.allclose(got, want, rtol=1e-5, atol=1e-5)
-    # the kernel's own definition: bias, then fmaf per tap in ascending order (an fma = exact product, one rounding)
-    w = conv.weight.detach().reshape(nk, ks).double().numpy(); b = conv.bias.detach().double().numpy()
-    xp = np.pad(x.numpy().astype(np.float64), ((0, 0), (ks // 2, ks // 2)))
-    acc = np.broadcast_to(b.astype(np.float32)[None, None, :], (x.shape[0], n_mels, nk)).copy()
-    for t in range(ks):
-        acc = (acc.astype(np.float64) + xp[:, t:t + n_mels, None] * w[None, None, :, t]).astype(np.float32)
-    assert np.array_equal(bits(got.numpy().reshape(x.shape[0], n_mels, nk)), bits(acc))
+    # the kernel's own definition: bias, then one exact fmaf per tap in ascending order (tests/row_ops_ref.py; a float64
+    # multiply-add narrowed afterwards rounds twice and is wrong on ties: tests/test_row_ops_ref.py)
+    from row_ops_ref import conv1d_mel_ref
+    ref = conv1d_mel_ref(x.numpy(), conv.weight.detach().reshape(nk, ks).numpy(), conv.bias.detach().numpy(), ks // 2)
+    assert np.array_equal(bits(got.numpy()), bits(ref))
 
 
 def test_new_entry_points_edges(be):
