@@ -338,8 +338,7 @@ int ap_begin(at_ctx* ctx, const char* who, int64_t ld_scores, int64_t ld_labels,
     const size_t b_keys = ap_align(8 * nkeys), b_recs = ap_align(sizeof(ap_tile_rec) * (size_t)cc * nt),
                  b_part = ap_align(8 * (size_t)cc * nt);
     // The slots are the context's: a call on another stream than the previous one waits for it (at_sum_f32's rule).
-    if (!ctx->ap_ev) AT_HIP(hipEventCreateWithFlags(&ctx->ap_ev, hipEventDisableTiming));
-    if (ctx->ap_used && ctx->ap_stream != stream) AT_HIP(hipStreamWaitEvent(stream, ctx->ap_ev, 0));
+    { const int rc = at_guard_enter(&ctx->guard[AT_GUARD_AP], stream); if (rc) return rc; }
     unsigned char* w = static_cast<unsigned char*>(at_ws(ctx, WS_AVG_PRECISION, 2 * b_keys + b_recs + b_part, stream));
     if (!w) return AT_E_NOMEM;
     plan->cc = cc;
@@ -378,11 +377,6 @@ int ap_chunk_terms(const ap_plan& plan, const uint64_t* sorted, int64_t n, int c
 }
 
 // behind the call's last launch
-int ap_end(at_ctx* ctx, hipStream_t stream) {
-    AT_HIP(hipEventRecord(ctx->ap_ev, stream));
-    ctx->ap_stream = stream;
-    ctx->ap_used = 1;
-    return AT_OK;
-}
+int ap_end(at_ctx* ctx, hipStream_t stream) { return at_guard_leave(&ctx->guard[AT_GUARD_AP], stream); }
 
 }  // namespace

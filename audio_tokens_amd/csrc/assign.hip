@@ -23,16 +23,15 @@
 #include <cstdlib>
 
 #include "at_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "chunked_sweep.h"
 
 namespace {
 
 constexpr int WG = 256;    // threads per workgroup (4 waves)
-constexpr int CN_PAD = 256;  // floats reserved per tile for the squared norms (whole 1 KiB pieces)
-
-__host__ __device__ constexpr int tile_rows(int na) { return 32 * na; }
+using cs::CN_PAD;      // floats reserved per tile for the squared norms (whole 1 KiB pieces)
+using cs::DC;          // features per chunk of the any-d image (chunked_sweep.h)
+using cs::dma_1k;
+using cs::tile_rows;
 __host__ __device__ constexpr int tile_floats(int dp, int na) { return tile_rows(na) * dp + CN_PAD; }
 
 // ---------------------------------------------------------------------------------------------
@@ -133,14 +132,6 @@ __device__ __forceinline__ void epilogue16_spec(float& bestd, unsigned& bestc, c
         bestd = bd;
         bestc = br != 16u ? (codebase | br) : bestc;
     }
-}
-
-// 1 KiB of global memory -> LDS without passing through registers (global_load_lds_dwordx4):
-// lane l's 16 bytes land at lds_wave_base + 16*l.
-__device__ __forceinline__ void dma_1k(const float* gsrc_lane, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)gsrc_lane,
-        (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -853,19 +844,18 @@ assign_mfma_pruned_reg_kernel(const float* __restrict__ X, long n, const float* 
 // centroid tile stay live across the chunks (so every inner product is still ONE ascending fmaf
 // chain); the centroid image is laid out [tile][chunk][row][64 swizzled] and streamed through LDS
 // one (tile, chunk) piece at a time; the x chunk of a wave's rows is re-read from L2 per piece.
-constexpr int DC = 64;  // features per chunk
-
+// The layout is chunked_sweep.h's, shared with the sweeps of knn.hip, ip.hip and rq.hip.
 __global__ void __launch_bounds__(WG) prep_centroids_chunked_kernel(const float* __restrict__ c, int k,
                                                                     int d, int nchunks, int na,
                                                                     float* __restrict__ img) {
     const int t = blockIdx.x;
     const int R = tile_rows(na);
-    float* out = img + (size_t)t * ((size_t)R * DC * nchunks + CN_PAD);
-    const int chunks16 = DC / 4;  // 16-byte chunks per row piece
+    float* out = img + (size_t)t * cs::tile_floats(na, nchunks);
+    const int chunks16 = DC / 4;  // 16-byte slots per row piece
     for (int e = threadIdx.x; e < nchunks * R * chunks16; e += WG) {
         const int ch = e / (R * chunks16);
         const int r = (e / chunks16) % R, pc = e % chunks16;
-        const int lc = pc ^ (r & 15);
+        const int lc = cs::chunk_slot(r, pc >> 1, pc & 1);   // the swizzle is an involution: slot pc holds logical slot lc
         const int q = lc >> 1, h = lc & 1;
         const int row = t * R + r;
         f32x4 v;
@@ -886,7 +876,7 @@ __global__ void __launch_bounds__(WG) prep_centroids_chunked_kernel(const float*
                 nrm = __builtin_fmaf(v, v, nrm);
             }
         }
-        out[(size_t)R * DC * nchunks + r] = nrm;
+        out[(size_t)cs::piece_floats(na) * nchunks + r] = nrm;
     }
 }
 
@@ -895,9 +885,8 @@ __global__ void __launch_bounds__(WG, WPS)
 assign_mfma_anyd_kernel(const float* __restrict__ X, long n, int d, int nchunks,
                         const float* __restrict__ img, int ntiles, long* __restrict__ ids,
                         float* __restrict__ dist) {
-    constexpr int R = tile_rows(NA);
-    constexpr int PIECE_F = R * DC;                 // floats of one (tile, chunk) piece
-    constexpr int BUF_F = PIECE_F + CN_PAD;         // + the norms behind the last chunk
+    constexpr int PIECE_F = cs::piece_floats(NA);   // floats of one (tile, chunk) piece
+    constexpr int BUF_F = cs::buf_floats(NA);       // + the norms behind the last chunk
     extern __shared__ __attribute__((aligned(16))) float smem[];  // 2 * BUF_F floats
 
     const int tid = threadIdx.x;
@@ -906,7 +895,7 @@ assign_mfma_anyd_kernel(const float* __restrict__ X, long n, int d, int nchunks,
     const int j = lane & 31;
     const int h = lane >> 5;
     const long row0 = ((long)blockIdx.x * 4 + wave) * (32 * NB);
-    const size_t tile_f = (size_t)PIECE_F * nchunks + CN_PAD;
+    const size_t tile_f = cs::tile_floats(NA, nchunks);
 
     const float* xrow[NB];
     float xn[NB];
@@ -987,7 +976,7 @@ assign_mfma_anyd_kernel(const float* __restrict__ X, long n, int d, int nchunks,
                 if (ch == 0) cacc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
                 for (int q = 0; q < DC / 8; q++) {
-                    const int pc = (2 * q + h) ^ swz;
+                    const int pc = (2 * q + h) ^ swz;   // cs::chunk_slot(j, q, h)
                     const f32x4 av = *reinterpret_cast<const f32x4*>(arow + pc * 4);
                     cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], xr[b][4 * q + 0], cacc, 0, 0, 0);
                     cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], xr[b][4 * q + 1], cacc, 0, 0, 0);
@@ -1134,13 +1123,13 @@ int launch_mfma(at_ctx* ctx, const float* x, int64_t n, const float* c, int k, i
 template <int NB, int NA, int WPS>
 static int launch_anyd(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k, int64_t* ids, float* dist,
                        hipStream_t stream) {
-    const int nchunks = (d + DC - 1) / DC;
+    const int nchunks = cs::nchunks_of(d);
     const int ntiles = (k + tile_rows(NA) - 1) / tile_rows(NA);
-    const size_t tile_f = (size_t)tile_rows(NA) * DC * nchunks + CN_PAD;
+    const size_t tile_f = cs::tile_floats(NA, nchunks);
     float* img = static_cast<float*>(at_ws(ctx, WS_CENT_IMG, sizeof(float) * ntiles * tile_f, stream));
     if (!img) return AT_E_NOMEM;
     AT_LAUNCH(prep_centroids_chunked_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, d, nchunks, NA, img);
-    const size_t lds = 2 * sizeof(float) * (tile_rows(NA) * DC + CN_PAD);
+    const size_t lds = 2 * sizeof(float) * cs::buf_floats(NA);
     AT_RAISE_LDS(ctx, (assign_mfma_anyd_kernel<NB, NA, WPS>), lds);
     const int64_t rows_per_wg = 4 * 32 * NB;
     AT_LAUNCH((assign_mfma_anyd_kernel<NB, NA, WPS>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
@@ -1150,14 +1139,10 @@ static int launch_anyd(at_ctx* ctx, const float* x, int64_t n, int d, const floa
 
 }  // namespace
 
-size_t at_chunked_image_tile_floats(int d, int na) {
-    return (size_t)tile_rows(na) * DC * ((d + DC - 1) / DC) + CN_PAD;
-}
-
 int at_prep_chunked_image(at_ctx* ctx, const float* c, int k, int d, int na, float* img, hipStream_t stream) {
     (void)ctx;
     const int ntiles = (k + tile_rows(na) - 1) / tile_rows(na);
-    AT_LAUNCH(prep_centroids_chunked_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, d, (d + DC - 1) / DC, na, img);
+    AT_LAUNCH(prep_centroids_chunked_kernel, dim3(ntiles), dim3(WG), 0, stream, c, k, d, cs::nchunks_of(d), na, img);
     return AT_OK;
 }
 

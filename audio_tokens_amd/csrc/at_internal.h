@@ -158,6 +158,24 @@ static inline void at_logmel_tables_clear(at_logmel_tables* t) {
     *t = at_logmel_tables{};
 }
 
+// Workspace slots that belong to the context and are written by every call of an entry: two calls on different streams
+// must not overlap in them, so a call on another stream than the previous one waits for it.
+struct at_ws_guard {
+    hipEvent_t ev;        // behind the last guarded call
+    hipStream_t stream;   // ... which ran here
+    int used;
+};
+enum at_guard_id {
+    AT_GUARD_SUM = 0,   // at_sum_f32: WS_REDUCE partials, WS_SUM_TICKET
+    AT_GUARD_SIL,       // at_silhouette_f32: WS_SILHOUETTE
+    AT_GUARD_KNN,       // at_knn_f32: WS_KNN_IMG, WS_KNN
+    AT_GUARD_AP,        // at_average_precision_f32 / at_ranking_metrics_f32: WS_AVG_PRECISION, WS_AVG_PRECISION_TMP
+    AT_GUARD_IP,        // at_assign_ip_f32 sweep: WS_IP_IMG
+    AT_GUARD_PQ,        // fused at_pq_encode_f32: WS_PQ_IMG
+    AT_GUARD_RQ,        // at_rq_encode_f32: WS_RQ_IMG, WS_RQ_TMP
+    AT_NGUARDS
+};
+
 struct at_ctx {
     int device;
     at_debug dbg;
@@ -191,25 +209,13 @@ struct at_ctx {
     // process-wide "already raised" flag would leave the second device of a process at the default limit)
     struct { const void* func; size_t bytes; } lds_raised[48];
     int n_lds_raised;
-    hipEvent_t sum_ev;        // behind the last at_sum_f32 launch (its partials and counter are per context)
-    hipStream_t sum_stream;
-    int sum_used;
-    hipEvent_t sil_ev;        // behind the last at_silhouette_f32 (its scratch, WS_SILHOUETTE, is per context)
-    hipStream_t sil_stream;
-    int sil_used;
-    hipEvent_t knn_ev;        // behind the last at_knn_f32 (WS_KNN_IMG / WS_KNN are per context)
-    hipStream_t knn_stream;
-    int knn_used;
-    hipEvent_t ap_ev;         // behind the last at_average_precision_f32 / at_ranking_metrics_f32 (WS_AVG_PRECISION / _TMP are per context)
-    hipStream_t ap_stream;
-    int ap_used;
-    hipEvent_t pq_ev;         // behind the last fused at_pq_encode_f32 (WS_PQ_IMG is per context)
-    hipStream_t pq_stream;
-    int pq_used;
-    hipEvent_t rq_ev;         // behind the last at_rq_encode_f32 (WS_RQ_IMG / WS_RQ_TMP are per context)
-    hipStream_t rq_stream;
-    int rq_used;
+    at_ws_guard guard[AT_NGUARDS];
 };
+
+// host.cpp.  enter: before the call touches the guarded slots (the event is created on first use, timing disabled; the
+// stream waits only when it is not the one of the previous call); leave: behind everything the call queued.
+int at_guard_enter(at_ws_guard* g, hipStream_t stream);
+int at_guard_leave(at_ws_guard* g, hipStream_t stream);
 
 // makes launches of `func` with `bytes` of dynamic LDS legal on the context's device (at most one runtime call per
 // kernel and size step; nothing below the default limit)
@@ -391,9 +397,8 @@ template <typename Clips>
 int at_logmel_any(at_ctx* ctx, const Clips& clips, int64_t n_frames, int sample_rate, int n_fft, int hop, int n_mels,
                   const float* fb_user_dev, float* out, int frame_major, hipStream_t stream);
 
-// assign.hip: the centroid image of the any-d sweep (tiles of 32 * na rows, features in chunks of 64, |c|^2 of a tile
-// behind its last chunk, +inf for rows >= k); at_chunked_image_tile_floats(d, na) floats per tile.  Used by knn.hip, ip.hip, rq.hip.
-size_t at_chunked_image_tile_floats(int d, int na);
+// assign.hip: builds the chunked centroid image of the any-d sweeps; its layout, at_chunked_image_tile_floats(d, na) and
+// the sweep over it that knn.hip, ip.hip and rq.hip share are in chunked_sweep.h.
 int at_prep_chunked_image(at_ctx* ctx, const float* c, int k, int d, int na, float* img, hipStream_t stream);
 
 int at_group_min_dist_f16(at_ctx* ctx, const float* c, int k, int d, const int32_t* cperm, int ng, float* dmin,

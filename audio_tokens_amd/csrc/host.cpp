@@ -183,12 +183,8 @@ void at_destroy(at_ctx* ctx) {
     if (ctx->side_stream) (void)AT_HIP_TOLERATE(hipStreamDestroy(ctx->side_stream));
     if (ctx->background_stream) (void)AT_HIP_TOLERATE(hipStreamDestroy(ctx->background_stream));
     if (ctx->mt_ready) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->mt_ready));
-    if (ctx->sum_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sum_ev));
-    if (ctx->sil_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->sil_ev));
-    if (ctx->knn_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->knn_ev));
-    if (ctx->pq_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->pq_ev));
-    if (ctx->rq_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->rq_ev));
-    if (ctx->ap_ev) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->ap_ev));
+    for (at_ws_guard& g : ctx->guard)
+        if (g.ev) (void)AT_HIP_TOLERATE(hipEventDestroy(g.ev));
     if (ctx->filter.host_misc) (void)AT_HIP_TOLERATE(hipHostFree(ctx->filter.host_misc));
     at_logmel_tables_clear(&ctx->lm_fb);
     at_logmel_tables_clear(&ctx->lm_any);
@@ -216,6 +212,19 @@ int64_t at_workspace_bytes(const at_ctx* ctx) {
 }
 
 }  // extern "C"
+
+int at_guard_enter(at_ws_guard* g, hipStream_t stream) {
+    if (!g->ev) AT_HIP(hipEventCreateWithFlags(&g->ev, hipEventDisableTiming));
+    if (g->used && g->stream != stream) AT_HIP(hipStreamWaitEvent(stream, g->ev, 0));
+    return AT_OK;
+}
+
+int at_guard_leave(at_ws_guard* g, hipStream_t stream) {
+    AT_HIP(hipEventRecord(g->ev, stream));
+    g->stream = stream;
+    g->used = 1;
+    return AT_OK;
+}
 
 int at_raise_lds(at_ctx* ctx, const void* func, size_t bytes) {
     if (bytes <= 32 * 1024) return AT_OK;

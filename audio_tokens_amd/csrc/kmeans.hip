@@ -223,13 +223,9 @@ int at_sum_f32(at_ctx* ctx, const float* v, int64_t n, double* out, void* stream
     // The partial buffer and the arrival counter are the context's: two calls on different streams must not overlap
     // (the wrong "last workgroup", a mixed sum, a counter that is never put back).  A call on another stream than the
     // previous one waits for it.
-    if (!ctx->sum_ev) AT_HIP(hipEventCreateWithFlags(&ctx->sum_ev, hipEventDisableTiming));
-    if (ctx->sum_used && ctx->sum_stream != stream) AT_HIP(hipStreamWaitEvent(stream, ctx->sum_ev, 0));
+    { const int rc = at_guard_enter(&ctx->guard[AT_GUARD_SUM], stream); if (rc) return rc; }
     AT_LAUNCH(sum_kernel, dim3(blocks), dim3(WG), 0, stream, v, (long)n, partial, ticket, out);
-    AT_HIP(hipEventRecord(ctx->sum_ev, stream));
-    ctx->sum_stream = stream;
-    ctx->sum_used = 1;
-    return AT_OK;
+    return at_guard_leave(&ctx->guard[AT_GUARD_SUM], stream);
 }
 
 int at_any_nonfinite_f32(at_ctx* ctx, const float* v, int64_t n, int32_t* flag, void* stream_) {

@@ -5,15 +5,13 @@
 //   clamp v < 0 ? 0 : v, which leaves a NaN a NaN; n < 20: the direct form sum (x-c)^2.
 // Listed: the k smallest finite (dis, j) in lexicographic order, ascending; the rest of a row is (-1, +inf).
 //
-// Fused path (2 <= k <= K_FUSED): the dense sweep of assign.hip with its running arg-min replaced by a running
-// per-lane top-KL list (KL = the power of two >= k, at least 4) in registers.  Centroids are staged through LDS by
-// LDS-DMA from the chunked centroid image (assign.hip, at_prep_chunked_image: tiles of 32*NA rows, 64 features per
-// chunk, |c|^2 of the tile behind its last chunk, +inf for pad rows); x rows stay in registers (d = 64, 128: one / two
-// chunks, template specialisations) or are re-read from L2 one chunk per stage (any other d that is a multiple of 4).
-// A finished accumulator gives each lane 16 candidates; the wave first compares their minimum with every lane's
-// KL-th key (one ballot) and then each candidate (one ballot each), so the insert network runs only for candidates
-// that improve some lane.  A lane sees its centroids in ascending index order ((tile, accumulator, register) is
-// ascending in j for a fixed half-wave), so a strict `<` insert that puts a candidate behind its equals keeps the
+// Fused path (2 <= k <= K_FUSED): the dense sweep over the chunked centroid image (chunked_sweep.h: the layout, the
+// LDS-DMA stream, the x side and the MFMA block; x rows in registers at d = 64, 128, re-read one chunk per stage at any
+// other d that is a multiple of 4), and what this kernel does with a finished tile: a running per-lane top-KL list
+// (KL = the power of two >= k, at least 4) in registers.  A finished accumulator gives each lane 16 candidates; the
+// wave first compares their minimum with every lane's KL-th key (one ballot) and then each candidate (one ballot
+// each), so the insert network runs only for candidates that improve some lane.  A lane sees its centroids in
+// ascending index order ((tile, accumulator, register) is ascending in j for a fixed half-wave), so a strict `<` insert that puts a candidate behind its equals keeps the
 // lexicographic (dis, j) order without comparing ids.  The two half-waves (same 32 rows, disjoint centroids) merge
 // once at the end: the elementwise (dis, j)-minimum of one list and the other reversed is a bitonic sequence of the
 // KL smallest, sorted by a bitonic merge network.
@@ -27,27 +25,15 @@
 #include <rocprim/rocprim.hpp>
 
 #include "at_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "chunked_sweep.h"
 
 namespace {
 
 constexpr int WG = 256;        // 4 waves
-constexpr int DC = 64;         // features per chunk of the centroid image
-constexpr int CN_PAD = 256;    // norms behind the last chunk of a tile (assign.hip)
 constexpr int NA = 4;          // 32-centroid accumulators per tile (128 centroids)
 constexpr int K_FUSED = 32;    // largest k of the fused path
 constexpr int64_t ROWS_PER_LAUNCH = (int64_t)1 << 30;
 constexpr size_t GENERAL_BYTES = (size_t)256 << 20;   // keys (in + out) of one block of the general path
-
-__device__ __forceinline__ void dma_1k(const float* gsrc_lane, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc_lane,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// the orc_assign clamp (a NaN stays a NaN and is never listed)
-__device__ __forceinline__ float clamp0(float v) { return v < 0.0f ? 0.0f : v; }
 
 // sort key of one distance: (bits << idbits) | j; non-finite -> all ones (sorts last, never listed)
 __device__ __forceinline__ uint64_t dis_key(float v, unsigned j, int idbits, uint64_t none) {
@@ -83,57 +69,20 @@ __global__ void __launch_bounds__(WG, WPS)
 knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const float* __restrict__ img, int ntiles,
                 int kc, int k, long* __restrict__ ids, float* __restrict__ dist, uint64_t* __restrict__ keys,
                 int idbits) {
-    constexpr int R = 32 * NA;
-    constexpr int PIECE_F = R * DC;
-    constexpr int BUF_F = PIECE_F + CN_PAD;
-    extern __shared__ __attribute__((aligned(16))) float smem[];  // 2 * BUF_F floats
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 31;   // x row within the wave's 32 rows == accumulator column
-    const int h = lane >> 5;   // which k of each MFMA k-pair this lane feeds
-    const long row0 = ((long)blockIdx.x * 4 + wave) * 32;
-    const int nch = NCH > 0 ? NCH : nchunks;
-    const size_t tile_f = (size_t)PIECE_F * nch + CN_PAD;
+    extern __shared__ __attribute__((aligned(16))) float smem[];  // 2 * cs::buf_floats(NA) floats
+    cs::Sweep<NA, NCH, true> sweep(img, smem, nchunks, ntiles);
+    const int j = sweep.j, h = sweep.h;
+    const long row0 = ((long)blockIdx.x * 4 + sweep.wave) * 32;
 
     long r = row0 + j;
     if (r >= n) r = n - 1;
-    const float* xrow = X + r * (long)(NCH > 0 ? NCH * DC : d);
-    float xn = 0.0f;
-    float xr[NCH > 0 ? NCH : 1][DC / 2];
-    auto load_x = [&](int chx, float (&xv)[DC / 2], int dd) {
-#pragma unroll
-        for (int q = 0; q < DC / 8; q++) {
-            const int f = chx * DC + 8 * q;
-            f32x4 u = {0, 0, 0, 0}, v = {0, 0, 0, 0};
-            if (f < dd) u = *reinterpret_cast<const f32x4*>(xrow + f);
-            if (f + 4 < dd) v = *reinterpret_cast<const f32x4*>(xrow + f + 4);
-            xv[4 * q + 0] = h ? u[1] : u[0];
-            xv[4 * q + 1] = h ? u[3] : u[2];
-            xv[4 * q + 2] = h ? v[1] : v[0];
-            xv[4 * q + 3] = h ? v[3] : v[2];
-        }
-    };
+    const int dd = NCH > 0 ? NCH * cs::DC : d;
+    const float* xrow = X + r * (long)dd;
+    const float xn = cs::sqnorm16(xrow, dd);
+    float xr[NCH > 0 ? NCH : 1][cs::DC / 2];
     if constexpr (NCH > 0) {
 #pragma unroll
-        for (int f = 0; f < NCH * DC; f += 4) {
-            const f32x4 u = *reinterpret_cast<const f32x4*>(xrow + f);
-            xn = __builtin_fmaf(u[0], u[0], xn);
-            xn = __builtin_fmaf(u[1], u[1], xn);
-            xn = __builtin_fmaf(u[2], u[2], xn);
-            xn = __builtin_fmaf(u[3], u[3], xn);
-        }
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++) load_x(ch, xr[ch], NCH * DC);
-    } else {
-        for (int f = 0; f < d; f += 4) {
-            const f32x4 u = *reinterpret_cast<const f32x4*>(xrow + f);
-            xn = __builtin_fmaf(u[0], u[0], xn);
-            xn = __builtin_fmaf(u[1], u[1], xn);
-            xn = __builtin_fmaf(u[2], u[2], xn);
-            xn = __builtin_fmaf(u[3], u[3], xn);
-        }
+        for (int ch = 0; ch < NCH; ch++) cs::load_x_chunk(xrow, ch, dd, h, xr[ch]);
     }
 
     float ld[KL];
@@ -141,53 +90,26 @@ knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const f
 #pragma unroll
     for (int s = 0; s < KL; s++) {
         ld[s] = __builtin_inff();
-        li[s] = 0xffffffffu;
+        li[s] = cs::NONE;
     }
     const long krow = row0 + j;                      // this lane's row (for the keys)
     const uint64_t none = idbits + 31 >= 64 ? ~0ull : ((1ull << (idbits + 31)) - 1ull);
 
-    auto stage_dma = [&](int ct, int ch, float* dst) {
-        const float* src = img + (size_t)ct * tile_f + (size_t)ch * PIECE_F;
-        const int pieces = (ch == nch - 1 ? BUF_F : PIECE_F) / 256;
-        for (int p = wave; p < pieces; p += 4) dma_1k(src + p * 256 + lane * 4, dst + p * 256);
-    };
-    stage_dma(0, 0, smem);
-    __syncthreads();
-
-    const int swz = j & 15;
-    const int nstages = ntiles * nch;
+    // The finished tile is handled inside the stage itself, not in a functor of cs::Sweep::run: with the top-k insert
+    // network behind a call boundary the compiler spends up to 24 more registers on the same instructions.
     f32x16 acc[NA];
-    auto stage = [&](int s, int ct, int ch, const float (&xv)[DC / 2]) {
-        const float* cur = smem + (s & 1) * BUF_F;
-        if (s + 1 < nstages) {
-            const bool wrap = ch + 1 == nch;
-            stage_dma(wrap ? ct + 1 : ct, wrap ? 0 : ch + 1, smem + ((s + 1) & 1) * BUF_F);
-        }
-#pragma unroll
-        for (int a = 0; a < NA; a++) {
-            const float* arow = cur + (a * 32 + j) * DC;
-            f32x16 cacc = acc[a];
-            if (ch == 0) cacc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int q = 0; q < DC / 8; q++) {
-                const int pc = (2 * q + h) ^ swz;
-                const f32x4 av = *reinterpret_cast<const f32x4*>(arow + pc * 4);
-                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], xv[4 * q + 0], cacc, 0, 0, 0);
-                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], xv[4 * q + 1], cacc, 0, 0, 0);
-                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], xv[4 * q + 2], cacc, 0, 0, 0);
-                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], xv[4 * q + 3], cacc, 0, 0, 0);
-            }
-            acc[a] = cacc;
-        }
-        if (ch == nch - 1) {
+    auto stage = [&](int s, int ct, int ch, const float (&xv)[cs::DC / 2]) {
+        const float* cur = sweep.begin_stage(smem, s, ct, ch);
+        sweep.mfma_piece(acc, cur, xv, ch == 0);
+        if (ch == sweep.nch - 1) {
+            const float* cnorm = cur + sweep.PIECE_F;   // the tile's norms
 #pragma unroll
             for (int a = 0; a < NA; a++) {
-                // accumulator register rr holds centroid idbase + (rr & 3) + 8 * (rr >> 2)
-                const unsigned idbase = (unsigned)(ct * NA + a) * 32u + 4u * (unsigned)h;
+                const unsigned idbase = (unsigned)cs::acc_base(ct * NA + a, h);
                 float u[16];
 #pragma unroll
                 for (int g = 0; g < 4; g++) {
-                    const f32x4 cn = *reinterpret_cast<const f32x4*>(cur + PIECE_F + a * 32 + 8 * g + 4 * h);
+                    const f32x4 cn = *reinterpret_cast<const f32x4*>(cnorm + a * 32 + 8 * g + 4 * h);
 #pragma unroll
                     for (int e = 0; e < 4; e++) u[4 * g + e] = __builtin_fmaf(-2.0f, acc[a][4 * g + e], xn + cn[e]);
                 }
@@ -195,11 +117,9 @@ knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const f
                     if (krow < n) {
                         uint64_t* kr = keys + krow * (long)kc;
 #pragma unroll
-                        for (int g = 0; g < 4; g++) {
-                            const unsigned j0 = idbase + 8u * g;
-#pragma unroll
-                            for (int e = 0; e < 4; e++)
-                                if (j0 + e < (unsigned)kc) kr[j0 + e] = dis_key(clamp0(u[4 * g + e]), j0 + e, idbits, none);
+                        for (int e = 0; e < 16; e++) {
+                            const unsigned id = idbase + (unsigned)cs::reg_offset(e);
+                            if (id < (unsigned)kc) kr[id] = dis_key(cs::clamp0(u[e]), id, idbits, none);
                         }
                     }
                 } else {
@@ -210,9 +130,9 @@ knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const f
                     if (__builtin_amdgcn_ballot_w64(m < ld[KL - 1]) != 0) {
 #pragma unroll
                         for (int e = 0; e < 16; e++) {
-                            const float cv = clamp0(u[e]);
+                            const float cv = cs::clamp0(u[e]);
                             if (__builtin_amdgcn_ballot_w64(cv < ld[KL - 1]) != 0)
-                                topk_insert<KL>(ld, li, cv, idbase + (unsigned)((e & 3) + 8 * (e >> 2)));
+                                topk_insert<KL>(ld, li, cv, idbase + (unsigned)cs::reg_offset(e));
                         }
                     }
                 }
@@ -220,19 +140,18 @@ knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const f
         }
         __syncthreads();
     };
-
+    sweep.prime();
     if constexpr (NCH > 0) {
-        static_assert(NCH <= 2, "x chunks held in registers: d = 64 or 128");
         for (int ct = 0; ct < ntiles; ct++) {   // (written out: a chunk index must be a constant here)
             stage(ct * NCH, ct, 0, xr[0]);
             if constexpr (NCH == 2) stage(ct * NCH + 1, ct, 1, xr[NCH - 1]);
         }
     } else {
         int ct = 0, ch = 0;
-        for (int s = 0; s < nstages; s++) {
-            load_x(ch, xr[0], d);
+        for (int s = 0; s < sweep.nstages; s++) {
+            cs::load_x_chunk(xrow, ch, d, h, xr[0]);
             stage(s, ct, ch, xr[0]);
-            if (++ch == nch) { ch = 0; ct++; }
+            if (++ch == sweep.nch) { ch = 0; ct++; }
         }
     }
 
@@ -268,7 +187,7 @@ knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const f
 #pragma unroll
             for (int s = 0; s < KL; s++) {
                 if (s < k) {
-                    const bool has = ci[s] != 0xffffffffu;
+                    const bool has = ci[s] != cs::NONE;
                     io[s] = has ? (long)ci[s] : -1L;
                     if (dout) dout[s] = has ? cd[s] : __builtin_inff();
                 }
@@ -303,7 +222,7 @@ knn_keys_scalar_kernel(const float* __restrict__ X, long n, int d, const float* 
             cn = __builtin_fmaf(cc[f], cc[f], cn);
             ip = __builtin_fmaf(xi[f], cc[f], ip);
         }
-        v = clamp0(__builtin_fmaf(-2.0f, ip, xn + cn));
+        v = cs::clamp0(__builtin_fmaf(-2.0f, ip, xn + cn));
     }
     const uint64_t none = (1ull << (idbits + 31)) - 1ull;
     keys[t] = dis_key(v, (unsigned)c, idbits, none);
@@ -340,9 +259,9 @@ template <int NCH, int KL, int MODE, int WPS>
 int launch_sweep(at_ctx* ctx, const float* x, int64_t n, int d, const float* img, int ntiles, int kc, int k,
                  int64_t* ids, float* dist, uint64_t* keys, int idbits, hipStream_t stream) {
     auto kern = &knn_mfma_kernel<NCH, KL, MODE, WPS>;
-    const size_t lds = 2 * sizeof(float) * (32 * NA * DC + CN_PAD);
+    const size_t lds = 2 * sizeof(float) * cs::buf_floats(NA);
     { const int rc = at_raise_lds(ctx, reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-    const int nchunks = (d + DC - 1) / DC;
+    const int nchunks = cs::nchunks_of(d);
     for (int64_t r0 = 0; r0 < n; r0 += ROWS_PER_LAUNCH) {
         const int64_t m = n - r0 < ROWS_PER_LAUNCH ? n - r0 : ROWS_PER_LAUNCH;
         AT_LAUNCH(kern, dim3((unsigned)((m + 127) / 128)), dim3(WG), lds, stream, x + r0 * d, (long)m, d, nchunks, img,
@@ -376,14 +295,13 @@ extern "C" int at_knn_f32(at_ctx* ctx, const float* x, int64_t n, int d, const f
     AT_HIP(hipSetDevice(ctx->device));
 
     // The workspace slots are the context's: a call on another stream than the previous one waits for it.
-    if (!ctx->knn_ev) AT_HIP(hipEventCreateWithFlags(&ctx->knn_ev, hipEventDisableTiming));
-    if (ctx->knn_used && ctx->knn_stream != stream) AT_HIP(hipStreamWaitEvent(stream, ctx->knn_ev, 0));
+    { const int grc = at_guard_enter(&ctx->guard[AT_GUARD_KNN], stream); if (grc) return grc; }
 
     const bool sweep = n >= 20 && d % 4 == 0 && at_aligned16(x);
     int rc = AT_OK;
     int idbits = 1;
     while ((1 << idbits) < kc) idbits++;
-    const int ntiles = (kc + 32 * NA - 1) / (32 * NA);
+    const int ntiles = (kc + cs::tile_rows(NA) - 1) / cs::tile_rows(NA);
     float* img = nullptr;
     if (sweep) {
         img = static_cast<float*>(at_ws(ctx, WS_KNN_IMG, sizeof(float) * ntiles * at_chunked_image_tile_floats(d, NA),
@@ -438,8 +356,6 @@ extern "C" int at_knn_f32(at_ctx* ctx, const float* x, int64_t n, int d, const f
         }
     }
     // behind everything this call queued: a later call on another stream waits for it
-    AT_HIP(hipEventRecord(ctx->knn_ev, stream));
-    ctx->knn_stream = stream;
-    ctx->knn_used = 1;
+    { const int grc = at_guard_leave(&ctx->guard[AT_GUARD_KNN], stream); if (grc) return grc; }
     return rc;
 }

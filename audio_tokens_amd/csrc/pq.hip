@@ -15,7 +15,8 @@
 // tile and sub-space a wave loads the sub-vectors of its 32 rows (both half-waves the same 16-byte pieces: every lane
 // needs the whole |x|^2 chain), while the loads of the next sub-space are already in flight, and sweeps the 256
 // centroids in two passes of four 32-centroid accumulators: dsub/2 MFMAs each, whose k order (group ascending, then
-// the two k-pairs, then k = 0, 1 inside an instruction) is the ascending chain of the contract, exactly as in knn.hip.
+// the two k-pairs, then k = 0, 1 inside an instruction) is the ascending chain of the contract, exactly as in
+// chunked_sweep.h.
 // The accumulator puts the x row on the lane and 16 centroids in its registers; a lane meets its centroids in
 // ascending index ((pass, accumulator, register) ascends for a fixed half-wave), so a running strict `<` minimum keeps
 // the lowest index without comparing ids.  The two half-waves (same rows, disjoint centroids) merge once per
@@ -25,9 +26,8 @@
 // General path (everything else): one thread per (row, sub-space) walks the codebook with the same scalar chains.
 // Decode: a gather, 16 bytes per thread where dsub and the pointers allow, one float per thread otherwise.
 #include "at_internal.h"
+#include "chunked_sweep.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
@@ -36,9 +36,8 @@ constexpr int KS = 256;                       // codebook rows of the fused path
 constexpr int WG = 256;                       // prep, general and decode kernels
 constexpr size_t LDS_BUDGET = 160 * 1024;     // the whole LDS of a CU: image + norms of d + M <= 160
 constexpr size_t LDS_TWO_WGS = 80 * 1024;     // up to here two workgroups of 8 waves share a CU, above one of 16
-constexpr unsigned NONE = 0xffffffffu;
-
-__device__ __forceinline__ float clamp0(float v) { return v < 0.0f ? 0.0f : v; }
+using cs::clamp0;
+using cs::NONE;
 
 // one workgroup per sub-space, one thread per codebook row
 __global__ void __launch_bounds__(KS)
@@ -94,6 +93,7 @@ pq_fused_kernel(const float* __restrict__ X, long n, int d, int M, int dsub_rt, 
         for (int g = 0; g < NG; g++) raw[g] = *reinterpret_cast<const f32x4*>(xrow + 4 * g);
     }
 
+    const cs::CodeSink sink{codes, dist, bad, pack4};
     for (; t < ntiles; t += tstride) {
         const long r = t * 32 + j;
         const bool store = h == 0 && r < n;
@@ -101,7 +101,7 @@ pq_fused_kernel(const float* __restrict__ X, long n, int d, int M, int dsub_rt, 
         unsigned pack = 0;
         for (int m = 0; m < M; m++) {
             const float* im = smem + (size_t)m * KS * (dsub + 1);
-            const float* cnp = im + KS * dsub;
+            const float* cnh = im + KS * dsub + 4 * h;   // the norms of this half-wave's centroids
             const float* xs = xrow + m * dsub;
             float xn = 0.0f;
             float xa[NG], xb[NG];
@@ -164,54 +164,17 @@ pq_fused_kernel(const float* __restrict__ X, long n, int d, int M, int dsub_rt, 
                             acc[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][1], xb0, acc[a], 0, 0, 0);
                     }
                 }
-                // accumulator register e holds centroid (p * 4 + a) * 32 + 4 * h + (e & 3) + 8 * (e >> 2): ascending in e
+                // accumulator register e holds centroid cs::acc_base(p * 4 + a, h) + cs::reg_offset(e): ascending in e
                 // (the fences keep the norm loads of all four accumulators from being hoisted above the products)
 #pragma unroll
                 for (int a = 0; a < 4; a++) {
                     __builtin_amdgcn_sched_barrier(0);
                     const int ab = p * 4 + a;
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const f32x4 cn = *reinterpret_cast<const f32x4*>(cnp + ab * 32 + 8 * q + 4 * h);
-#pragma unroll
-                        for (int e = 0; e < 4; e++) {
-                            const float v = clamp0(__builtin_fmaf(-2.0f, acc[a][4 * q + e], xn + cn[e]));
-                            const bool lt = v < best;   // false for a NaN and for +inf
-                            best = lt ? v : best;
-                            bcode = lt ? (unsigned)(ab * 16 + 4 * q + e) : bcode;
-                        }
-                    }
+                    cs::min16(acc[a], cnh + ab * 32, xn, (unsigned)(ab * 16), best, bcode);
                 }
             }
-
-            // merge the half-waves: the smaller distance, the lower index on equal distances (NONE is the highest)
-            unsigned idx = NONE;
-            if (bcode != NONE) {
-                const unsigned e = bcode & 15u;
-                idx = (bcode >> 4) * 32u + (e & 3u) + 8u * (e >> 2) + 4u * (unsigned)h;
-            }
-            const float ov = __shfl_xor(best, 32);
-            const unsigned oi = (unsigned)__shfl_xor((int)idx, 32);
-            if (ov < best || (ov == best && oi < idx)) {
-                best = ov;
-                idx = oi;
-            }
-            const bool none = idx == NONE;   // best is still +inf
-            if (none) idx = 0u;
-            if (store) {
-                const long o = r * (long)M + m;
-                if (dist) dist[o] = best;
-                if (none && bad) *bad = 1;
-                if (pack4) {
-                    pack |= idx << (8 * (m & 3));
-                    if ((m & 3) == 3) {
-                        *reinterpret_cast<unsigned*>(codes + o - 3) = pack;
-                        pack = 0;
-                    }
-                } else {
-                    codes[o] = (uint8_t)idx;
-                }
-            }
+            const unsigned win = cs::merged_index(best, bcode, h);
+            sink.put(win, best, store, r * (long)M + m, m, pack);
         }
         xrow = xnext;
     }
@@ -304,20 +267,6 @@ int launch_fused(at_ctx* ctx, const float* x, int64_t n, int d, int M, const flo
     return AT_OK;
 }
 
-// calls of one context share WS_PQ_IMG: a call on another stream than the previous one waits for it
-int pq_enter(at_ctx* ctx, hipStream_t stream) {
-    if (!ctx->pq_ev) AT_HIP(hipEventCreateWithFlags(&ctx->pq_ev, hipEventDisableTiming));
-    if (ctx->pq_used && ctx->pq_stream != stream) AT_HIP(hipStreamWaitEvent(stream, ctx->pq_ev, 0));
-    return AT_OK;
-}
-
-int pq_leave(at_ctx* ctx, hipStream_t stream) {
-    AT_HIP(hipEventRecord(ctx->pq_ev, stream));
-    ctx->pq_stream = stream;
-    ctx->pq_used = 1;
-    return AT_OK;
-}
-
 }  // namespace
 
 extern "C" int at_pq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, int M, int ksub, const float* codebooks,
@@ -335,7 +284,7 @@ extern "C" int at_pq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, i
     const int dsub = d / M;
     const size_t lds = sizeof(float) * KS * ((size_t)d + M);
     if (ksub == KS && dsub % 4 == 0 && at_aligned16(x) && n >= 20 && lds <= LDS_BUDGET) {
-        int rc = pq_enter(ctx, stream);
+        int rc = at_guard_enter(&ctx->guard[AT_GUARD_PQ], stream);   // calls of one context share WS_PQ_IMG
         if (rc) return rc;
         float* img = static_cast<float*>(at_ws(ctx, WS_PQ_IMG, lds, stream));
         if (!img) return AT_E_NOMEM;
@@ -345,7 +294,7 @@ extern "C" int at_pq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, i
         else if (dsub == 16) rc = launch_fused<16>(ctx, x, n, d, M, img, lds, codes, dist, bad, stream);
         else rc = launch_fused<0>(ctx, x, n, d, M, img, lds, codes, dist, bad, stream);
         if (rc) return rc;
-        return pq_leave(ctx, stream);
+        return at_guard_leave(&ctx->guard[AT_GUARD_PQ], stream);
     }
     AT_LAUNCH(pq_general_kernel, dim3((unsigned)((n * M + WG - 1) / WG)), dim3(WG), 0, stream, x, (long)n, d, M, dsub,
               ksub, codebooks, n < 20 ? 1 : 0, codes, dist, bad);

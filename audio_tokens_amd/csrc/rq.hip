@@ -8,12 +8,12 @@
 // r_{m+1}[i][f] = r_m[i][f] - codebooks[m][codes[i][m]][f], one fp32 subtraction (a flagged row subtracts row 0).
 //
 // Fused path (d = 64 or 128, 16-byte aligned rows, codebooks and residual, n >= 20): one launch for all M stages.  The
-// codebooks are prepared once per call into the chunked centroid image of the any-d sweeps (assign.hip,
-// at_prep_chunked_image: tiles of 128 rows, 64 features per chunk, |c|^2 of a tile behind its last chunk, +inf for pad
-// rows, so ksub < 256 needs no masking) in WS_RQ_IMG: stage m owns the tiles m * tps .. m * tps + tps - 1, tps =
-// ceil(ksub / 128) -- at ksub = 256 the [M * 256][d] table is one image.  A wave owns 32 rows and the four waves of a
-// workgroup share the tiles, which stream through double-buffered LDS by LDS-DMA exactly as in knn.hip / ip.hip; the
-// piece behind the last one of stage m is the first of stage m + 1, so the stream never stalls on the residual update.
+// codebooks are prepared once per call into the chunked centroid image (chunked_sweep.h; at_prep_chunked_image: tiles
+// of 128 rows, 64 features per chunk, |c|^2 of a tile behind its last chunk, +inf for pad rows, so ksub < 256 needs no
+// masking) in WS_RQ_IMG: stage m owns the tiles m * tps .. m * tps + tps - 1, tps = ceil(ksub / 128) -- at ksub = 256
+// the [M * 256][d] table is one image.  A wave owns 32 rows and the four waves of a workgroup share the tiles, which
+// stream through double-buffered LDS by LDS-DMA (cs::Sweep, chunked_sweep.h); the piece behind the last one of stage m
+// is the first of stage m + 1, so the stream never stalls on the residual update.
 // Per stage: v_mfma_f32_32x32x2_f32 over the features in ascending order (the chain of the contract), the
 // fma(-2, acc, rn + cn) epilogue with the clamp, a running strict `<` minimum over centroids met in ascending index
 // ((tile, accumulator, register) ascends for a fixed half-wave), one merge of the two half-waves (same rows, disjoint
@@ -31,24 +31,14 @@
 // Decode: out = codebooks[0][codes[.][0]], then + codebooks[m][codes[.][m]] for m = 1 .. M-1 in ascending order, one
 // fp32 addition each; 16 bytes per thread where d and the pointers allow.  A code >= ksub makes the row NaN.
 #include "at_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "chunked_sweep.h"
 
 namespace {
 
 constexpr int WG = 256;        // 4 waves
-constexpr int DC = 64;         // features per chunk of the centroid image
-constexpr int CN_PAD = 256;    // norms behind the last chunk of a tile (assign.hip)
 constexpr int NA = 4;          // 32-centroid accumulators per tile (128 centroids)
-constexpr unsigned NONE = 0xffffffffu;
-
-__device__ __forceinline__ void dma_1k(const float* gsrc_lane, float* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc_lane,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ float clamp0(float v) { return v < 0.0f ? 0.0f : v; }
+using cs::clamp0;
+using cs::NONE;
 
 // d = 64 * NCH; tps tiles of the image per stage
 template <int NCH>
@@ -56,142 +46,41 @@ __global__ void __launch_bounds__(WG, 2)
 rq_fused_kernel(const float* __restrict__ X, long n, int M, int ksub, int tps, const float* __restrict__ img,
                 const float* __restrict__ cb, uint8_t* __restrict__ codes, float* __restrict__ dist,
                 float* __restrict__ resid, int* __restrict__ bad, int pack4) {
+    constexpr int DC = cs::DC;
     constexpr int D = NCH * DC;
-    constexpr int R = 32 * NA;
-    constexpr int PIECE_F = R * DC;
-    constexpr int BUF_F = PIECE_F + CN_PAD;
-    constexpr size_t TILE_F = (size_t)PIECE_F * NCH + CN_PAD;
     static_assert(NCH == 1 || NCH == 2, "the residual stays in registers: d = 64 or 128");
-    extern __shared__ __attribute__((aligned(16))) float smem[];  // 2 * BUF_F floats
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 31;   // row within the wave's 32 rows == accumulator column
-    const int h = lane >> 5;   // which k of each MFMA k-pair this lane feeds
-    const long ro = ((long)blockIdx.x * 4 + wave) * 32 + j;
+    extern __shared__ __attribute__((aligned(16))) float smem[];  // 2 * cs::buf_floats(NA) floats
+    // the tiles of all stages are contiguous in the image: one stream, stage m its tiles m * tps .. m * tps + tps - 1
+    cs::Sweep<NA, NCH, true> sweep(img, smem, NCH, M * tps);
+    const int j = sweep.j, h = sweep.h;
+    const long ro = ((long)blockIdx.x * 4 + sweep.wave) * 32 + j;
     const long r = ro < n ? ro : n - 1;
     const bool store = h == 0 && ro < n;
 
     // the residual: register i of chunk ch holds feature 64 ch + 2 i + h; rn its |r|^2 chain over all D features
+    const float* xrow = X + r * (long)D;
     float xr[NCH][DC / 2];
-    float rn = 0.0f;
-    {
-        const float* xrow = X + r * (long)D;
+    float rn = cs::sqnorm16(xrow, D);
 #pragma unroll
-        for (int ch = 0; ch < NCH; ch++) {
-#pragma unroll
-            for (int q = 0; q < DC / 8; q++) {
-                const f32x4 u = *reinterpret_cast<const f32x4*>(xrow + ch * DC + 8 * q);
-                const f32x4 v = *reinterpret_cast<const f32x4*>(xrow + ch * DC + 8 * q + 4);
-#pragma unroll
-                for (int e = 0; e < 4; e++) rn = __builtin_fmaf(u[e], u[e], rn);
-#pragma unroll
-                for (int e = 0; e < 4; e++) rn = __builtin_fmaf(v[e], v[e], rn);
-                xr[ch][4 * q + 0] = h ? u[1] : u[0];
-                xr[ch][4 * q + 1] = h ? u[3] : u[2];
-                xr[ch][4 * q + 2] = h ? v[1] : v[0];
-                xr[ch][4 * q + 3] = h ? v[3] : v[2];
-            }
-        }
-    }
+    for (int ch = 0; ch < NCH; ch++) cs::load_x_chunk(xrow, ch, D, h, xr[ch]);
 
-    // piece s of the stream: chunk s % NCH of tile s / NCH (the tiles of all stages are contiguous in the image)
-    const int npieces = M * tps * NCH;
-    auto stage_dma = [&](int s, float* dst) {
-        const int ct = s / NCH, ch = s % NCH;
-        const float* src = img + (size_t)ct * TILE_F + (size_t)ch * PIECE_F;
-        const int pieces = (ch == NCH - 1 ? BUF_F : PIECE_F) / 256;
-        for (int p = wave; p < pieces; p += 4) dma_1k(src + p * 256 + lane * 4, dst + p * 256);
-    };
-    stage_dma(0, smem);
-    __syncthreads();
-
-    const int swz = j & 15;
-    float best = __builtin_inff();
-    unsigned bcode = NONE;   // (tile of the stage * NA + accumulator) * 16 + register
+    sweep.prime();
+    const cs::CodeSink sink{codes, dist, bad, pack4};
     f32x16 acc[NA];
-    auto piece = [&](int s, int t, int ch, const float (&xv)[DC / 2]) {
-        const float* cur = smem + (s & 1) * BUF_F;
-        if (s + 1 < npieces) stage_dma(s + 1, smem + ((s + 1) & 1) * BUF_F);
-#pragma unroll
-        for (int a = 0; a < NA; a++) {
-            const float* arow = cur + (a * 32 + j) * DC;
-            f32x16 cacc = acc[a];
-            if (ch == 0) cacc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int q = 0; q < DC / 8; q++) {
-                const int pc = (2 * q + h) ^ swz;
-                const f32x4 av = *reinterpret_cast<const f32x4*>(arow + pc * 4);
-                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], xv[4 * q + 0], cacc, 0, 0, 0);
-                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], xv[4 * q + 1], cacc, 0, 0, 0);
-                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], xv[4 * q + 2], cacc, 0, 0, 0);
-                cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], xv[4 * q + 3], cacc, 0, 0, 0);
-            }
-            acc[a] = cacc;
-        }
-        if (ch == NCH - 1) {
-            // accumulator register e holds centroid (t * NA + a) * 32 + 4 * h + (e & 3) + 8 * (e >> 2): ascending in e
-#pragma unroll
-            for (int a = 0; a < NA; a++) {
-                const unsigned codebase = (unsigned)(t * NA + a) * 16u;
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const f32x4 cn = *reinterpret_cast<const f32x4*>(cur + PIECE_F + a * 32 + 8 * g + 4 * h);
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const float v = clamp0(__builtin_fmaf(-2.0f, acc[a][4 * g + e], rn + cn[e]));
-                        const bool lt = v < best;   // false for a NaN and for +inf
-                        best = lt ? v : best;
-                        bcode = lt ? codebase + (unsigned)(4 * g + e) : bcode;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    };
-
     unsigned pack = 0;
-    int s = 0;
 #pragma unroll 1
     for (int m = 0; m < M; m++) {
-        best = __builtin_inff();
-        bcode = NONE;
-#pragma unroll 1
-        for (int t = 0; t < tps; t++) {   // (written out: a chunk index must be a constant here)
-            piece(s, t, 0, xr[0]);
-            if constexpr (NCH == 2) piece(s + 1, t, 1, xr[NCH - 1]);
-            s += NCH;
-        }
-
-        // merge the half-waves: the smaller distance, the lower index on equal distances (NONE is the highest)
-        unsigned idx = NONE;
-        if (bcode != NONE) {
-            const unsigned e = bcode & 15u;
-            idx = (bcode >> 4) * 32u + (e & 3u) + 8u * (e >> 2) + 4u * (unsigned)h;
-        }
-        const float ov = __shfl_xor(best, 32);
-        const unsigned oi = (unsigned)__shfl_xor((int)idx, 32);
-        if (ov < best || (ov == best && oi < idx)) {
-            best = ov;
-            idx = oi;
-        }
-        const bool none = idx == NONE;   // best is still +inf
-        if (none) idx = 0u;
-        if (store) {
-            const long o = ro * (long)M + m;
-            if (dist) dist[o] = best;
-            if (none && bad) *bad = 1;
-            if (pack4) {
-                pack |= idx << (8 * (m & 3));
-                if ((m & 3) == 3) {
-                    *reinterpret_cast<unsigned*>(codes + o - 3) = pack;
-                    pack = 0;
-                }
-            } else {
-                codes[o] = (uint8_t)idx;
-            }
-        }
+        float best = __builtin_inff();
+        unsigned bcode = cs::NONE;   // (tile of the stage * NA + accumulator) * 16 + register
+        const int t0 = m * tps;
+        sweep.run(t0, t0 + tps, acc, xr, xrow, D, [&](int ct, const float* cnorm, const f32x16 (&acc)[NA]) {
+            const float* cnh = cnorm + 4 * h;   // the norms of this half-wave's centroids
+#pragma unroll
+            for (int a = 0; a < NA; a++)
+                cs::min16(acc[a], cnh + a * 32, rn, (unsigned)((ct - t0) * NA + a) * 16u, best, bcode);
+        });
+        const unsigned win = cs::merged_index(best, bcode, h);
+        const unsigned idx = sink.put(win, best, store, ro * (long)M + m, m, pack);
         if (m + 1 == M && !resid) break;
 
         // r <- r - word (idx < ksub: a pad row's +inf norm never wins), and the |r|^2 chain of the new residual
@@ -400,12 +289,12 @@ rq_decode_scalar_kernel(const uint8_t* __restrict__ codes, long n, int d, int M,
 template <int NCH>
 int launch_fused(at_ctx* ctx, const float* x, int64_t n, int M, int ksub, const float* cb, uint8_t* codes, float* dist,
                  float* resid, int32_t* bad, hipStream_t stream) {
-    const int d = NCH * DC;
-    const int tps = (ksub + 32 * NA - 1) / (32 * NA);
+    const int d = NCH * cs::DC;
+    const int tps = (ksub + cs::tile_rows(NA) - 1) / cs::tile_rows(NA);
     const size_t tile_f = at_chunked_image_tile_floats(d, NA);
     float* img = static_cast<float*>(at_ws(ctx, WS_RQ_IMG, sizeof(float) * (size_t)M * tps * tile_f, stream));
     if (!img) return AT_E_NOMEM;
-    if (ksub % (32 * NA) == 0) {   // the [M * ksub][d] table is one image whose tiles m * tps .. are stage m
+    if (ksub % cs::tile_rows(NA) == 0) {   // the [M * ksub][d] table is one image whose tiles m * tps .. are stage m
         const int rc = at_prep_chunked_image(ctx, cb, M * ksub, d, NA, img, stream);
         if (rc) return rc;
     } else {
@@ -415,7 +304,7 @@ int launch_fused(at_ctx* ctx, const float* x, int64_t n, int M, int ksub, const 
             if (rc) return rc;
         }
     }
-    const size_t lds = 2 * sizeof(float) * (32 * NA * DC + CN_PAD);
+    const size_t lds = 2 * sizeof(float) * cs::buf_floats(NA);
     AT_RAISE_LDS(ctx, rq_fused_kernel<NCH>, lds);
     const int pack4 = M % 4 == 0 && (reinterpret_cast<uintptr_t>(codes) & 3u) == 0;
     AT_LAUNCH(rq_fused_kernel<NCH>, dim3((unsigned)((n + 127) / 128)), dim3(WG), lds, stream, x, (long)n, M, ksub, tps, img,
@@ -432,20 +321,6 @@ int encode_general(at_ctx* ctx, const float* x, int64_t n, int d, int M, int ksu
     }
     AT_LAUNCH(rq_general_kernel, dim3((unsigned)((n + RB - 1) / RB)), dim3(WG), 0, stream, x, (long)n, d, M, ksub, cb,
               n < 20 ? 1 : 0, res, codes, dist, bad);
-    return AT_OK;
-}
-
-// calls of one context share WS_RQ_IMG / WS_RQ_TMP: a call on another stream than the previous one waits for it
-int rq_enter(at_ctx* ctx, hipStream_t stream) {
-    if (!ctx->rq_ev) AT_HIP(hipEventCreateWithFlags(&ctx->rq_ev, hipEventDisableTiming));
-    if (ctx->rq_used && ctx->rq_stream != stream) AT_HIP(hipStreamWaitEvent(stream, ctx->rq_ev, 0));
-    return AT_OK;
-}
-
-int rq_leave(at_ctx* ctx, hipStream_t stream) {
-    AT_HIP(hipEventRecord(ctx->rq_ev, stream));
-    ctx->rq_stream = stream;
-    ctx->rq_used = 1;
     return AT_OK;
 }
 
@@ -468,7 +343,7 @@ extern "C" int at_rq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, i
     AT_HIP(hipSetDevice(ctx->device));
     if (bad) AT_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), stream));
 
-    int rc = rq_enter(ctx, stream);
+    int rc = at_guard_enter(&ctx->guard[AT_GUARD_RQ], stream);   // calls of one context share WS_RQ_IMG / WS_RQ_TMP
     if (rc) return rc;
     if ((d == 64 || d == 128) && n >= 20 && at_aligned16(x) && at_aligned16(codebooks) && at_aligned16(residual)) {
         if (d == 64) rc = launch_fused<1>(ctx, x, n, M, ksub, codebooks, codes, dist, residual, bad, stream);
@@ -477,7 +352,7 @@ extern "C" int at_rq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, i
         rc = encode_general(ctx, x, n, d, M, ksub, codebooks, codes, dist, residual, bad, stream);
     }
     if (rc) return rc;
-    return rq_leave(ctx, stream);
+    return at_guard_leave(&ctx->guard[AT_GUARD_RQ], stream);
 }
 
 extern "C" int at_rq_decode_f32(at_ctx* ctx, const uint8_t* codes, int64_t n, int d, int M, int ksub,

@@ -224,8 +224,7 @@ extern "C" int at_silhouette_f32(at_ctx* ctx, const float* x, int d, const int64
                  b_nrm = sil_align(8 * un), b_tmp = sil_align(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
     const size_t total = b_keys + 4 * b_u32 + b_off + b_nrm + b_tmp;
     // The slot is the context's: a call on another stream than the previous one waits for it (at_sum_f32's rule).
-    if (!ctx->sil_ev) AT_HIP(hipEventCreateWithFlags(&ctx->sil_ev, hipEventDisableTiming));
-    if (ctx->sil_used && ctx->sil_stream != stream) AT_HIP(hipStreamWaitEvent(stream, ctx->sil_ev, 0));
+    { const int rc = at_guard_enter(&ctx->guard[AT_GUARD_SIL], stream); if (rc) return rc; }
     unsigned char* w = static_cast<unsigned char*>(at_ws(ctx, WS_SILHOUETTE, total, stream));
     if (!w) return AT_E_NOMEM;
     int64_t* keys = reinterpret_cast<int64_t*>(w);
@@ -246,8 +245,6 @@ extern "C" int at_silhouette_f32(at_ctx* ctx, const float* x, int d, const int64
     AT_RAISE_LDS(ctx, silhouette_kernel, LDS_BYTES);
     AT_LAUNCH(silhouette_kernel, dim3((unsigned)((n + QW - 1) / QW)), dim3(WG), LDS_BYTES, stream, x, d, n, perm, seg, off,
               nrm, s);
-    AT_HIP(hipEventRecord(ctx->sil_ev, stream));
-    ctx->sil_stream = stream;
-    ctx->sil_used = 1;
+    { const int rc = at_guard_leave(&ctx->guard[AT_GUARD_SIL], stream); if (rc) return rc; }
     return at_sum_f32(ctx, s, n, sum, stream);
 }

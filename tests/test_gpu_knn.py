@@ -45,6 +45,9 @@ GRID = [
     (1280, 7, 2, 4097), (1280, 256, 256, 19), (640, 500, 5, 1), (64, 1, 2, 4097), (128, 1, 4, 19),
     (50, 256, 16, 20), (8, 500, K_FUSED, 19), (640, 500, K_FUSED + 1, 4097), (128, 256, 100, 20),
     (64, 500, 503, 20), (640, 7, 16, 4097),
+    # the list lengths the rows above leave out at a width, at the edges of the sweep: a second workgroup with one live
+    # row, a second tile with one real centroid, a second chunk of one 16-byte piece (d = 68), three chunks (d = 192)
+    (64, 129, 16, 129), (128, 129, 3, 129), (128, 300, 8, 129), (68, 129, 8, 129), (192, 129, K_FUSED, 129),
 ]
 
 

@@ -12,8 +12,8 @@ from rq_ref import rq_decode_ref, rq_encode_ref
 pytestmark = pytest.mark.gpu
 
 # (d, M): fused at d = 64 (one chunk) and 128 (two); general (one at_assign_f32 per stage) everywhere else: d = 8, 12,
-# 32 (any-d sweep), 50 (scalar sweep: d % 4 != 0), 640 (ten chunks)
-SHAPES = [(64, 1), (64, 2), (64, 8), (128, 4), (8, 3), (12, 2), (50, 2), (32, 4), (640, 2)]
+# 32 (any-d sweep), 50 (scalar sweep: d % 4 != 0), 640 (ten chunks); M = 5: more than four stages, codes stored as bytes
+SHAPES = [(64, 1), (64, 2), (64, 5), (64, 8), (128, 4), (8, 3), (12, 2), (50, 2), (32, 4), (640, 2)]
 NS = [1, 19, 20, 31, 32, 33, 127, 128, 129, 4097]
 OFFS = (4, 16, 32, 128)   # register, accumulator, half-wave / 32-centroid and 128-centroid (tile) boundaries
 
@@ -148,7 +148,7 @@ def test_rq_non_finite_and_degenerate(be, oracle, n, d):
     assert np.array_equal(bits(_np(got[2])[keep]), bits(ref0[2][keep]))
 
 
-@pytest.mark.parametrize("ksub", [1, 7, 255])
+@pytest.mark.parametrize("ksub", [1, 7, 129, 255])   # 129: a second tile with one real word
 def test_rq_small_codebooks(be, oracle, ksub):
     for d, M in ((64, 3), (128, 2), (12, 3)):
         x, cb = _data(ksub, 300, d, M, ksub)

@@ -18,7 +18,10 @@ pytestmark = pytest.mark.gpu
 GRID = [(64, 1, 1), (64, 5, 19), (64, 33, 33), (64, 129, 257), (64, 300, 1000),
         (128, 130, 300), (128, 600, 200),
         (8, 7, 100), (32, 40, 70), (200, 70, 65), (640, 33, 40),
-        (6, 10, 50), (7, 3, 21)]
+        (6, 10, 50), (7, 3, 21),
+        # a second workgroup with one live row and a second tile with one real centroid at every form of the sweep;
+        # a second chunk of one 16-byte piece (d = 68), three chunks (d = 192)
+        (64, 129, 129), (128, 129, 129), (68, 129, 129), (192, 129, 129)]
 FAMILY_SHAPES = [(64, 129, 257), (128, 130, 300), (200, 70, 65)]
 
 
@@ -135,6 +138,30 @@ def test_rows_off_a_16_byte_boundary_give_the_aligned_bits(be):
     assert view.data_ptr() % 16 == 4 and view.is_contiguous()
     ids, ip = be.assign_ip(view, be.from_host(c))
     assert np.array_equal(ids.cpu().numpy(), ids_r) and np.array_equal(bits(ip.cpu().numpy()), bits(ip_r))
+
+
+def test_assign_ip_two_streams_at_once(be):
+    """Two calls with different centroid tables on two streams of one backend share the context's centroid image
+    (WS_IP_IMG): the later one waits for the earlier one, and both give the single-stream bits.  This cannot prove the
+    absence of a race; it pins the guarded path, and runs in milliseconds."""
+    rng = np.random.default_rng(77)
+    x1, c1 = _near_centroids(rng, 64, 300, 4096)
+    x2, c2 = _near_centroids(rng, 64, 170, 4100)
+    t = [be.from_host(a) for a in (x1, c1, x2, c2)]
+    want = [be.assign_ip(t[0], t[1]), be.assign_ip(t[2], t[3])]
+    torch.cuda.synchronize(be.device)
+    s1, s2 = torch.cuda.Stream(be.device), torch.cuda.Stream(be.device)
+    s1.wait_stream(torch.cuda.current_stream(be.device))
+    s2.wait_stream(torch.cuda.current_stream(be.device))
+    with torch.cuda.stream(s1):
+        r1 = be.assign_ip(t[0], t[1])
+    with torch.cuda.stream(s2):
+        r2 = be.assign_ip(t[2], t[3])
+    with torch.cuda.stream(s1):
+        r3 = be.assign_ip(t[0], t[1])
+    torch.cuda.synchronize(be.device)
+    for got, ref in zip((r1, r2, r3), (want[0], want[1], want[0])):
+        assert torch.equal(got[0], ref[0]) and torch.equal(got[1].view(torch.int32), ref[1].view(torch.int32))
 
 
 def test_want_dist_false(be):
