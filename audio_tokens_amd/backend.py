@@ -139,6 +139,16 @@ class HostHelpers:
         tot = {name: int(totals[0][name]) for name, _ in _lib.FRONTEND_TOTALS_FIELDS}
         return plan, order, groups[:tot["n_groups"]], tot
 
+    def dct_matrix(self, n_mfcc: int, n_mels: int, norm="ortho") -> np.ndarray:
+        """at_dct_matrix_host: the DCT-II table [n_mels, n_mfcc] of ops.MFCC, cos(pi / n_mels * (n + 0.5) * k) in double,
+        scaled (norm "ortho": column 0 by 1/sqrt(2), then all by sqrt(2 / n_mels); None: all by 2), rounded to float32
+        once."""
+        if norm not in ("ortho", None):
+            raise ValueError('norm must be "ortho" or None')
+        out = np.empty((n_mels, n_mfcc), np.float32)
+        _lib.check(self.lib.at_dct_matrix_host(n_mfcc, n_mels, 1 if norm == "ortho" else 0, _np_ptr(out)))
+        return out
+
     @staticmethod
     def part_layout(k, d):
         """Packed per-rank partial of one Lloyd iteration, in floats: sums [k*d], counts [k], padding to an even
@@ -695,6 +705,64 @@ class HipBackend(HostHelpers):
         with torch.cuda.device(self.device):
             _lib.check(self.lib.at_rq_decode_f32(self.ctx.handle, _ptr(codes), n, d, M, ksub, _ptr(cb), _ptr(out),
                                                  self._stream()))
+        return out
+
+    def _frame_prefix(self, n_frames, total):
+        """Per-clip frame counts -> the device prefix [n_clips + 1] (int64) of at_mfcc_f32 / at_deltas_f32: one upload."""
+        counts = np.asarray(n_frames, dtype=np.int64).reshape(-1)
+        if (counts < 0).any() or int(counts.sum()) != total:
+            raise ValueError(f"the clips hold {int(counts.sum())} frames, the rows {total}")
+        prefix = np.zeros(counts.size + 1, np.int64)
+        np.cumsum(counts, out=prefix[1:])
+        return torch.from_numpy(prefix).to(self.device), counts.size
+
+    def mfcc(self, rows, n_frames, n_mfcc=40, dct=None, orders=0, win_length=5, top_db=None, frame_major=True,
+             norm="ortho", out=None):
+        """MFCC and delta features of log-mel rows (at_mfcc_f32): rows [n, n_mels] frame-major, as logmel(...,
+        frame_major=True) and frontend_ragged leave them; n_frames: the frames of every clip, in order (they add up to
+        n; zeros allowed) -> [n, D] (frame_major) or flat [n * D] with clip i a [D, T_i] block at D * first_frame[i];
+        D = n_mfcc * (1 + orders), feature o * n_mfcc + k.  top_db: None, or the per-clip clamp of amplitude_to_DB;
+        dct: the caller's table [n_mels, n_mfcc] (default: dct_matrix(n_mfcc, n_mels, norm), kept on the device).
+        The prefix is built on the host from n_frames: one small upload, nothing is read back."""
+        rows = self._f32(rows)
+        assert rows.dim() == 2, "mfcc: rows must be [n, n_mels]"
+        n, n_mels = rows.shape
+        prefix, n_clips = self._frame_prefix(n_frames, n)
+        if dct is None:
+            cache = self.__dict__.setdefault("_dct_tables", {})
+            key = (int(n_mfcc), int(n_mels), norm)
+            if key not in cache:
+                cache[key] = self.from_host(self.dct_matrix(int(n_mfcc), int(n_mels), norm))
+            dct = cache[key]
+        else:
+            dct = self._f32(dct)
+            if tuple(dct.shape) != (n_mels, n_mfcc):
+                raise ValueError(f"mfcc: dct must be [n_mels, n_mfcc] = [{n_mels}, {n_mfcc}], got {tuple(dct.shape)}")
+        D = int(n_mfcc) * (1 + int(orders)) if 0 <= int(orders) <= 2 else int(n_mfcc)
+        if out is None:
+            out = self.empty((n, D) if frame_major else (n * D,))
+        else:
+            assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == n * D
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_mfcc_f32(
+                self.ctx.handle, _ptr(rows), _ptr(prefix), n_clips, n, n_mels, int(n_mfcc), _ptr(dct), int(orders),
+                int(win_length), 0 if top_db is None else 1, 0.0 if top_db is None else float(top_db), _ptr(out),
+                _lib.AT_LAYOUT_FRAME_MAJOR if frame_major else _lib.AT_LAYOUT_MEL_MAJOR, self._stream()))
+        return out
+
+    def deltas(self, rows, n_frames, win_length=5, out=None):
+        """The delta operator of mfcc() alone (at_deltas_f32): rows [n, F] frame-major, n_frames as for mfcc -> [n, F]."""
+        rows = self._f32(rows)
+        assert rows.dim() == 2, "deltas: rows must be [n, F]"
+        n, F = rows.shape
+        prefix, n_clips = self._frame_prefix(n_frames, n)
+        if out is None:
+            out = self.empty((n, F))
+        else:
+            assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == n * F
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_deltas_f32(self.ctx.handle, _ptr(rows), _ptr(prefix), n_clips, n, F, int(win_length),
+                                              _ptr(out), self._stream()))
         return out
 
     def assign_hinted(self, x, c, hint_ids, order=None, want_dist=True):

@@ -91,6 +91,8 @@ enum at_ws_slot {
     WS_PQ_IMG,         // at_pq_encode_f32: MFMA-operand image of the M codebooks + their |c|^2 (pq.hip)
     WS_RQ_IMG,         // at_rq_encode_f32: chunked centroid image of the M stage codebooks (at_prep_chunked_image)
     WS_RQ_TMP,         // at_rq_encode_f32 general path: the running residual, when the caller takes none
+    WS_MFCC_MAX,       // at_mfcc_f32 with top_db: one ordered key per clip, the maximum of its log-mel values (mfcc.hip)
+    WS_MFCC_DCT,       // at_mfcc_f32 without a caller's table: the table of at_dct_matrix_host for (mfcc_dct_nmfcc, mfcc_dct_nmels)
     WS_NSLOTS
 };
 
@@ -173,6 +175,7 @@ enum at_guard_id {
     AT_GUARD_IP,        // at_assign_ip_f32 sweep: WS_IP_IMG
     AT_GUARD_PQ,        // fused at_pq_encode_f32: WS_PQ_IMG
     AT_GUARD_RQ,        // at_rq_encode_f32: WS_RQ_IMG, WS_RQ_TMP
+    AT_GUARD_MFCC,      // at_mfcc_f32 with top_db or without a caller's table: WS_MFCC_MAX, WS_MFCC_DCT
     AT_NGUARDS
 };
 
@@ -210,6 +213,7 @@ struct at_ctx {
     struct { const void* func; size_t bytes; } lds_raised[48];
     int n_lds_raised;
     at_ws_guard guard[AT_NGUARDS];
+    int mfcc_dct_nmfcc, mfcc_dct_nmels;   // what WS_MFCC_DCT holds (0 = nothing)
 };
 
 // host.cpp.  enter: before the call touches the guarded slots (the event is created on first use, timing disabled; the

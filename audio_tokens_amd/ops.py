@@ -20,6 +20,8 @@
         (processors/spectrogram_generator.py:99)
     get_spectrogram + get_sequence                        ->  AudioTokenizer
         (tools/manual_tester.py: audio -> tokens against a trained vocabulary)
+    torchaudio.transforms.MFCC, ComputeDeltas             ->  MFCC, ComputeDeltas
+        (not used by the reference: the 13 + delta + delta-delta features of HTK / Kaldi-style tokenisers)
 
 Same constructor arguments, method names, return types and error behaviour as the originals for the
 subset the reference uses.  All arithmetic happens in libaudio_tokens_amd.so (HIP, gfx950); this
@@ -46,7 +48,7 @@ from .backend import default_backend
 __all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "IndexFlatIP", "normalize_rows", "silhouette_samples",
            "silhouette_score", "average_precision", "mean_average_precision", "roc_auc", "mean_roc_auc",
            "roc_auc_score", "d_prime", "f1_score", "hamming_loss", "classification_metrics", "load_flac",
-           "load_flac_batch", "AudioTokenizer", "ProductQuantizer", "ResidualQuantizer"]
+           "load_flac_batch", "AudioTokenizer", "ProductQuantizer", "ResidualQuantizer", "MFCC", "ComputeDeltas"]
 
 
 def _is_host(x) -> bool:
@@ -146,6 +148,115 @@ class LogMelSpectrogram:
         be = self.backend
         return be.logmel(be._f32(waveform), self.sample_rate, self.n_fft, self.hop_length, self.n_mels,
                          fb=self.fb, frame_major=True, l2norm=l2norm)
+
+
+class MFCC:
+    """torchaudio.transforms.MFCC(sample_rate, n_mfcc, dct_type, norm, log_mels, melkwargs) on the device, with
+    ComputeDeltas folded in: log-mel (LogMelSpectrogram's kernels), the per-clip top_db clamp of AmplitudeToDB, the
+    DCT-II and `deltas` orders of time differences (0, 1 or 2; win_length as in ComputeDeltas, mode "replicate") in one
+    kernel behind the log-mel call (HipBackend.mfcc, at_mfcc_f32; the arithmetic contract: DESIGN.md section 6k).
+
+    __call__(waveform [..., L]) -> [..., D, T], D = n_mfcc * (1 + deltas), feature o * n_mfcc + k for order o.
+    top_db=None, deltas=0 is the DCT of exactly what LogMelSpectrogram returns.  top_db clamps every clip at its OWN
+    maximum - top_db (torchaudio takes one maximum over a whole [B, L] batch; the reference calls its transforms clip by
+    clip).  dct: the caller's table [n_mels, n_mfcc], e.g. torchaudio.functional.create_dct's, in place of the
+    library's, which evaluates the cosines in double.  dct_type other than 2 raises ValueError as torchaudio does;
+    log_mels=True raises NotImplementedError (the log-mel kernels store dB only).
+    A width with D % 4 != 0 (13 + delta + delta-delta = 39) sends the nearest-centroid searches down their general
+    paths; 40, or 13 and a zero column, would take the 16-byte ones.  Padding is the caller's business."""
+
+    def __init__(self, sample_rate=22050, n_mfcc=40, n_fft=512, hop_length=128, n_mels=64, dct_type=2, norm="ortho",
+                 log_mels=False, top_db=80.0, deltas=0, win_length=5, dct=None, fb=None, backend=None):
+        if dct_type != 2:
+            raise ValueError(f"DCT type not supported: {dct_type}")
+        if log_mels:
+            raise NotImplementedError("log_mels=True: the log-mel kernels store dB only")
+        if norm not in ("ortho", None):
+            raise ValueError('norm must be "ortho" or None')
+        if not 1 <= n_mfcc <= n_mels:
+            raise ValueError("Cannot select more MFCC coefficients than # mel bins")
+        if deltas not in (0, 1, 2):
+            raise ValueError(f"deltas must be 0, 1 or 2, got {deltas}")
+        if win_length < 3 or win_length % 2 == 0:
+            raise ValueError(f"win_length must be odd and >= 3, got {win_length}")
+        if top_db is not None and not top_db >= 0:
+            raise ValueError("top_db must be positive value")
+        self.sample_rate, self.n_fft, self.hop_length, self.n_mels = sample_rate, n_fft, hop_length, n_mels
+        self.n_mfcc, self.norm, self.top_db, self.deltas, self.win_length = n_mfcc, norm, top_db, deltas, win_length
+        self.D = n_mfcc * (1 + deltas)
+        self.backend = be = backend or default_backend()
+        self.fb = None if fb is None else be._f32(fb)
+        self.dct = None if dct is None else be._f32(dct)
+        if self.dct is not None and tuple(self.dct.shape) != (n_mels, n_mfcc):
+            raise ValueError(f"dct must be [n_mels, n_mfcc] = [{n_mels}, {n_mfcc}], got {tuple(self.dct.shape)}")
+        self.last_bad = None
+
+    def to(self, device):
+        return self
+
+    def of_rows(self, rows, n_frames, frame_major=True):
+        """The features of log-mel rows [n, n_mels] that are already on the device (HipBackend.mfcc's arguments)."""
+        return self.backend.mfcc(rows, n_frames, n_mfcc=self.n_mfcc, dct=self.dct, orders=self.deltas,
+                                 win_length=self.win_length, top_db=self.top_db, frame_major=frame_major, norm=self.norm)
+
+    def _logmel_rows(self, waveform):
+        be = self.backend
+        w = be._f32(waveform)
+        w2 = w.reshape(-1, w.shape[-1])
+        rows = be.logmel(w2, self.sample_rate, self.n_fft, self.hop_length, self.n_mels, fb=self.fb, frame_major=True)
+        return rows, w.shape[:-1], w2.shape[0]
+
+    def __call__(self, waveform):
+        rows, lead, n_clips = self._logmel_rows(waveform)
+        T = rows.shape[0] // max(n_clips, 1)
+        out = self.of_rows(rows, [T] * n_clips, frame_major=False)
+        return out.reshape(*lead, self.D, T)
+
+    def batch(self, waveforms, sample_rates=None):
+        """LogMelSpectrogram.batch for these features: clips of any length, channel count and sample rate -> a list of
+        [D, T_i] views of one flat device tensor, None where a clip is too short for the reflect padding.
+        self.last_bad: the front end's per-clip flags (a NaN or Inf in the clip's log-mel)."""
+        be = self.backend
+        rates = self.sample_rate if sample_rates is None else sample_rates
+        rows, T, first, self.last_bad = be.frontend_ragged(waveforms, rates, self.sample_rate, self.n_fft, self.hop_length,
+                                                           self.n_mels, fb=self.fb, frame_major=True)
+        out = self.of_rows(rows, T, frame_major=False)
+        D = self.D
+        return [None if T[i] == 0 else out[D * int(first[i]): D * (int(first[i]) + int(T[i]))].view(D, int(T[i]))
+                for i in range(len(T))]
+
+    def frames(self, waveform, l2norm=False):
+        """[n_clips, L] -> frame-major [n_clips * T, D] (optionally row-normalised): the matrix Kmeans.train takes."""
+        rows, _, n_clips = self._logmel_rows(waveform)
+        out = self.of_rows(rows, [rows.shape[0] // max(n_clips, 1)] * n_clips)
+        return self.backend.l2norm_rows(out) if l2norm else out
+
+
+class ComputeDeltas:
+    """torchaudio.transforms.ComputeDeltas(win_length, mode="replicate") on the device (HipBackend.deltas,
+    at_deltas_f32): [..., F, T] -> the same shape.  The regression form of DESIGN.md section 6k, equal to torchaudio's
+    in exact arithmetic; a constant input and T = 1 give exactly +0.  Any other mode raises ValueError."""
+
+    def __init__(self, win_length=5, mode="replicate", backend=None):
+        if mode != "replicate":
+            raise ValueError(f'mode "{mode}" is not supported: only "replicate"')
+        if win_length < 3 or win_length % 2 == 0:
+            raise ValueError(f"win_length must be odd and >= 3, got {win_length}")
+        self.win_length, self.mode = win_length, mode
+        self.backend = backend or default_backend()
+
+    def to(self, device):
+        return self
+
+    def __call__(self, specgram):
+        be = self.backend
+        x = be._f32(specgram)
+        assert x.dim() >= 2, "ComputeDeltas: [..., F, T]"
+        F, T = x.shape[-2], x.shape[-1]
+        x3 = x.reshape(-1, F, T)
+        rows = x3.transpose(1, 2).reshape(-1, F)
+        out = be.deltas(rows, [T] * x3.shape[0], win_length=self.win_length)
+        return out.reshape(x3.shape[0], T, F).transpose(1, 2).contiguous().reshape(x.shape)
 
 
 class Resample:
@@ -1056,10 +1167,32 @@ class AudioTokenizer:
     n_mels * num_kernels with `conv`, the nn.Conv1d(1, num_kernels, kernel_size, padding) of config.use_convolution.
     normalize: config.normalize, the per-clip (spec - min) / (max - min).  One batch is one ragged front-end call
     (frame-major rows; unit rows and the scaling in the same log-mel call), the convolution and its row normalisation if
-    any, one nearest-centroid search, and two device->host copies: the tokens and the per-clip flags."""
+    any, one nearest-centroid search, and two device->host copies: the tokens and the per-clip flags.
+    AudioTokenizer.from_features(centroids, features): an ops.MFCC instance replaces the log-mel rows by its features
+    between the front-end call and the search (frontend_ragged without unit rows, HipBackend.mfcc, l2norm_rows, the
+    search); the vocabulary is then [k, D] with D = features.D."""
 
     def __init__(self, centroids, sample_rate=22050, n_fft=512, hop_length=128, n_mels=64, normalize=False, conv=None,
                  fb=None, backend=None):
+        self._setup(centroids, sample_rate, n_fft, hop_length, n_mels, normalize, conv, fb, backend, None)
+
+    @classmethod
+    def from_features(cls, centroids, features, normalize=False, conv=None, fb=None, backend=None):
+        """The tokenizer of a vocabulary trained on `features` (an ops.MFCC instance): sample rate, transform size, hop
+        and n_mels of the front end are the instance's own, and so are fb and the backend unless given.  (A constructor
+        of its own rather than one more keyword: tests/test_audio_tokens_abi.py pins the argument list of __init__.)  conv has
+        no meaning here and raises ValueError."""
+        if conv is not None:
+            raise ValueError("AudioTokenizer: features and conv cannot be combined")
+        if not isinstance(features, MFCC):
+            raise ValueError("AudioTokenizer: features must be an ops.MFCC instance")
+        self = cls.__new__(cls)
+        self._setup(centroids, features.sample_rate, features.n_fft, features.hop_length, features.n_mels, normalize, None,
+                    features.fb if fb is None else fb, backend or features.backend, features)
+        return self
+
+    def _setup(self, centroids, sample_rate, n_fft, hop_length, n_mels, normalize, conv, fb, backend, features):
+        self.features = features
         self.backend = be = backend or default_backend()
         if isinstance(centroids, IndexFlatL2):
             self.index = centroids
@@ -1070,7 +1203,7 @@ class AudioTokenizer:
         self.sample_rate, self.n_fft, self.hop_length, self.n_mels = sample_rate, n_fft, hop_length, n_mels
         self.normalize, self.conv = bool(normalize), conv
         self.fb = None if fb is None else be._f32(fb)
-        d = n_mels * (conv.weight.shape[0] if conv is not None else 1)
+        d = n_mels * (conv.weight.shape[0] if conv is not None else 1) if features is None else features.D
         assert self.index.d == d, f"centroids are [k, {self.index.d}], the frames [n, {d}]"
         self.last_tokens = None   # device int64: the tokens of the last batch's kept clips, clip after clip
 
@@ -1087,10 +1220,13 @@ class AudioTokenizer:
             return []
         rates = self.sample_rate if sample_rates is None else sample_rates
         rows, T, first, bad = be.frontend_ragged(waveforms, rates, self.sample_rate, self.n_fft, self.hop_length, self.n_mels,
-                                                 fb=self.fb, frame_major=True, l2norm=self.conv is None,
+                                                 fb=self.fb, frame_major=True,
+                                                 l2norm=self.conv is None and self.features is None,
                                                  minmax=self.normalize)
         if rows.shape[0] == 0:
             return [None] * n
+        if self.features is not None:
+            rows = be.l2norm_rows(self.features.of_rows(rows, T))
         if self.conv is not None:
             with torch.no_grad():
                 bias = self.conv.bias.detach() if self.conv.bias is not None else None

@@ -20,6 +20,8 @@
  *   faiss.IndexFlatIP(d).search(x, 1), Kmeans(spherical=True) (likewise)   at_assign_ip_f32, at_renorm_rows_f32
  *   faiss.ProductQuantizer(d, M, 8).compute_codes(x) / .decode(codes) (likewise)  at_pq_encode_f32, at_pq_decode_f32
  *   greedy residual quantiser (RVQ, beam 1; the library's own contract)    at_rq_encode_f32, at_rq_decode_f32
+ *   torchaudio.transforms.MFCC / ComputeDeltas on log-mel rows (likewise)  at_mfcc_f32, at_deltas_f32,
+ *                                                                          at_dct_matrix_host
  *   faiss.Kmeans(d, k, niter).train(x, init_centroids)                     at_rand_perm_mt19937,
  *       processors/cluster_creator.py:42-56                                at_gather_rows_f32,
  *                                                                          at_assign_f32, at_assign_hinted_f32,
@@ -564,6 +566,40 @@ int at_rq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, int M, int k
  * out are 16-byte aligned, one float per thread otherwise.  No workspace. */
 int at_rq_decode_f32(at_ctx* ctx, const uint8_t* codes, int64_t n, int d, int M, int ksub, const float* codebooks,
                      float* out, void* stream);
+
+/* ---- MFCC and delta features of log-mel rows (torchaudio.transforms.MFCC, ComputeDeltas; csrc/mfcc.hip) ----------
+ * Input: log-mel rows x[g][n], frame-major [n_frames][n_mels] fp32, as at_logmel_f32 / at_logmel_ragged_f32 leave them,
+ * and a DEVICE prefix first_frame[n_clips + 1] (int64, exclusive, non-decreasing, first_frame[0] = 0, last entry =
+ * n_frames): clip i owns the frames [first_frame[i], first_frame[i + 1]); empty clips are allowed.
+ *   top_db (use_top_db != 0): floor_i = (max over every value of clip i) - top_db, one fp32 subtraction; every value v
+ *     of the clip becomes v < floor_i ? floor_i : v; a clip that holds a NaN becomes NaN throughout.  The maximum is per
+ *     clip, always: amplitude_to_DB on a clip passed alone (torchaudio takes one maximum over a whole [B, L] batch).
+ *   DCT table: dct[n][k], [n_mels][n_mfcc]; null = the table of at_dct_matrix_host(n_mfcc, n_mels, 1, .), built on the
+ *     host and uploaded by the call.
+ *   coefficients: c[g][k] = the fp32 fmaf chain over n = 0 .. n_mels - 1, ascending, from +0:
+ *     acc = fmaf(x[g][n], dct[n][k], acc).
+ *   deltas: win_length odd and >= 3, N = (win_length - 1) / 2; for frame t of a clip with T frames, acc = +0, then for
+ *     j = 1 .. N ascending acc = fmaf((float)j, c[clamp(t + j)] - c[clamp(t - j)], acc), the difference one fp32
+ *     subtraction, clamp to [0, T - 1] of the frame's own clip; delta[t] = acc / denom, one IEEE fp32 division, denom =
+ *     (float)(N (N + 1) (2N + 1) / 3).  (compute_deltas with mode="replicate" in exact arithmetic; a constant clip and
+ *     T = 1 give exactly +0.)  The second order is the same operator applied to the first.  orders: 0, 1 or 2.
+ *   out: D = n_mfcc * (1 + orders) features per frame, feature o * n_mfcc + k.  AT_LAYOUT_FRAME_MAJOR: [n_frames][D];
+ *     AT_LAYOUT_MEL_MAJOR (feature-major): clip i is a contiguous [D][T_i] block at D * first_frame[i] floats.
+ *   A NaN or Inf frame gives NaN coefficients by the chain's own arithmetic and reaches at most orders * N frames on
+ *   either side through the deltas, never another clip.  No flag is set by this call.
+ * One launch (top_db: a memset and a small reduction launch in front of it, the per-clip maxima in a workspace slot of
+ * the context: a call on another stream than the context's previous top_db call waits for it).  16-byte stores where
+ * D % 4 == 0, the layout is frame-major and out is 16-byte aligned.  n_frames == 0 or n_clips == 0: nothing is launched.
+ * Errors: null pointers, win_length even or < 3 (checked whatever `orders` is), orders outside 0..2, n_mfcc outside
+ * [1, n_mels], n_mels outside the log-mel range, top_db < 0 (or NaN) when used, a window whose halo does not fit in LDS
+ * beside n_mels-wide rows (win_length <= 9 fits at every width). */
+int at_dct_matrix_host(int n_mfcc, int n_mels, int ortho, float* dct_host);
+int at_mfcc_f32(at_ctx* ctx, const float* logmel, const int64_t* first_frame, int64_t n_clips, int64_t n_frames,
+                int n_mels, int n_mfcc, const float* dct_or_null, int orders, int win_length, int use_top_db,
+                float top_db, float* out, int layout, void* stream);
+/* The delta operator alone: rows [n_frames][F] -> out [n_frames][F], delta[t] as above over the rows of each clip. */
+int at_deltas_f32(at_ctx* ctx, const float* rows, const int64_t* first_frame, int64_t n_clips, int64_t n_frames, int F,
+                  int win_length, float* out, void* stream);
 
 /* ---- FLAC: torchaudio.load(path) for the reference's .flac files (processors/spectrogram_generator.py:99) --------
  * Native FLAC streams of 1-8 channels and 4-24 bits per sample.  The host finds the frames, the device decodes them:
