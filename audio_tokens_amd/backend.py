@@ -167,6 +167,17 @@ class HostHelpers:
                                                    ctypes.byref(ns)))
         return int(ns.value)
 
+    # What a backend may fuse, composed from what every backend has.
+    def lloyd_stats_split(self, hassign, cent, n: int, nsplit_out, parts, stats_row, objs=None) -> None:
+        """lloyd_stats followed by split_clusters_device."""
+        k, d = cent.shape
+        self.lloyd_stats(hassign, parts, k, d, stats_row, objs=objs)
+        self.split_clusters_device(hassign, cent, n, nsplit_out)
+
+    def from_host_async(self, a, dtype=None):
+        """from_host that need not drain the stream first."""
+        return self.from_host(a, dtype)
+
 
 class HipBackend(HostHelpers):
     def __init__(self, device=None):

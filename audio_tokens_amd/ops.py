@@ -377,6 +377,127 @@ class _Dist:
         return self._all_reduce(v, self.dist.ReduceOp.SUM) if self.on else v
 
 
+class _TrainingSet:
+    """What one Kmeans.train() iterates over: `xs`, this rank's rows of the (global) training subsample of `ns` rows,
+    and -- sharded -- `pos`, their positions in it (ascending; None in a single process)."""
+
+    def __init__(self, be, dist, xs, ns, pos):
+        self.be, self.dist, self.xs, self.ns, self.pos = be, dist, xs, ns, pos
+
+    def rows_at(self, positions):
+        """Rows of the (global) subsample at `positions` [m] -> device [m, d], on every rank."""
+        be, dist, xs, pos = self.be, self.dist, self.xs, self.pos
+        positions = np.asarray(positions, dtype=np.int64)
+        if not dist.on:
+            return be.gather_rows(xs, positions.astype(np.int32))
+        out = be.zeros((len(positions), xs.shape[1]))
+        want = be.from_host(positions)
+        if pos.numel():
+            j = torch.searchsorted(pos, want).clamp_(max=pos.numel() - 1)
+            ok = pos[j] == want
+            if bool(ok.any()):
+                out[ok] = be.gather_rows(xs, j[ok].to(torch.int32).contiguous())
+        return dist.sum_bits(out)
+
+
+class _PrunedSweep:
+    """The exact pruned search of one Kmeans.train() (d = 64 / 128: csrc/prune.hip) and the host schedule around it.
+
+    The sweep skips by a spatial grouping of the centroids, `cperm`, computed on the host (group_rows_kd).  The
+    grouping only decides how much the exact sweep can skip, never a result, so it may be of older centroids:
+      - a cold start groups its initial centroids before it can begin, and regroups once they have settled
+        (iteration 2);
+      - a warm start begins with the grouping the previous train() ended with (`begin_with`) while the host regroups
+        the new initial centroids beside the first iterations (`regroup`; not when it continues from that training's
+        own result: the grouping is of centroids a few iterations older than these, nothing to redo);
+      - a last regrouping near the end (late_due) is what the next warm start and the tokeniser's index begin with.
+    A regrouping runs on the helper thread (_grouper) and is taken up by the first search queued after it is done.
+
+    The host queues an iteration several times faster than the device runs it.  Left alone it would be a whole
+    training ahead, and a regrouping -- which needs the device to have reached the centroids it groups, plus ~3 ms
+    of host work -- would arrive after the host had queued every iteration that could have used it.  So the host
+    stays at most AHEAD iterations ahead (waiting on an event that many iterations old: the device always has
+    queued work) and measures the device's iteration time, `iter_ms`, from those events."""
+
+    AHEAD = 3
+    # what the path calls on a backend beyond the dense path's methods and HostHelpers' defaults
+    NEEDS = ("assign_pruned", "assign_c2f", "group_min_dist", "group_means", "group_neighbours", "visit_order",
+             "visit_order_beside", "sum_beside", "centroid_accum_join", "to_host_async", "record_event_timed")
+
+    @classmethod
+    def applies(cls, be, d, k, rows) -> bool:
+        return (all(hasattr(be, name) for name in cls.NEEDS) and d in (64, 128) and k >= 1024 and (k + 31) // 32 <= 512
+                and rows >= 4096)
+
+    def __init__(self, be, k, niter, cent, cold, begin_with=None, regroup=False):
+        self.be, self.k, self.niter, self.cold = be, k, niter, cold
+        self.regrouping = None   # host grouping of newer centroids, under way on the helper thread
+        self.regrouping_is_late = False
+        self.paced = collections.deque()
+        self.iter_ms = self.last_done = None
+        if begin_with is None:
+            self.cperm = be.from_host(be.group_rows_kd(be.to_host(cent)))
+        else:
+            self.cperm = begin_with
+            if regroup:
+                self.regrouping = self._regroup_beside(cent)
+
+    def _regroup_beside(self, c):
+        """Host grouping of the centroids `c` on the helper thread; the copy to the host is queued on the
+        stream and waited for there, not here."""
+        be = self.be
+        h, ready = be.to_host_async(c)
+
+        def job():
+            ready.synchronize()
+            return be.group_rows_kd(h.numpy())
+        return _grouper().submit(job)
+
+    def late_due(self, it) -> bool:
+        """Whether the last regrouping should be under way at iteration `it`: from niter - 6 on, or earlier when the
+        iterations left take the device no more than 4.5 ms (short iterations, a shard of an N-GPU run: submitted
+        early enough to be finished when the last iteration is), never in the first half, never below 10 iterations."""
+        niter = self.niter
+        if niter < 10 or it < niter // 2:
+            return False
+        return it >= niter - 6 or (self.iter_ms is not None and (niter - it) * self.iter_ms <= 4.5)
+
+    def search(self, it, xs, cent, vorder):
+        """Queues iteration `it`'s exact search over the centroids `cent` -> (ids, dis).  vorder: the visiting order
+        made from the previous iteration's answer (Kmeans._accumulate), None in iteration 0."""
+        be = self.be
+        if self.regrouping is not None and self.regrouping.done():
+            self.cperm = be.from_host_async(self.regrouping.result())   # (the small table goes up without draining the stream)
+            self.regrouping = None
+        elif (it == 2 and self.cold and self.regrouping is None) or (self.late_due(it) and not self.regrouping_is_late):
+            # cold start: regroup once the centroids have settled (taken up when the host is done); near the end:
+            # for the next warm start and the tokeniser (replaces one still under way: these centroids are newer)
+            self.regrouping_is_late = self.late_due(it)
+            self.regrouping = self._regroup_beside(cent)
+        dmin = be.group_min_dist(cent, self.cperm)
+        if vorder is None:   # no previous assignment yet: coarse-to-fine exact search
+            gnbr = be.group_neighbours(be.group_means(cent, self.cperm), 8)
+            return be.assign_c2f(xs, cent, self.cperm, dmin, gnbr)
+        return be.assign_pruned(xs, cent, vorder, self.cperm, dmin, image_current=True)
+
+    def iteration_queued(self):
+        """Behind everything an iteration queues: marks it with an event and waits for the iteration AHEAD before."""
+        self.paced.append(self.be.record_event_timed())
+        if len(self.paced) > self.AHEAD:
+            done = self.paced.popleft()
+            done.synchronize()
+            if self.last_done is not None:
+                self.iter_ms = self.last_done.elapsed_time(done)
+            self.last_done = done
+
+    def final_grouping(self):
+        """The grouping the training ends with: the late regrouping, submitted early enough to be done or about to be
+        (waits for it), else any that is done, else the one in use."""
+        if self.regrouping is not None and (self.regrouping.done() or self.regrouping_is_late):
+            self.cperm = self.be.from_host_async(self.regrouping.result())
+        return self.cperm
+
+
 class Kmeans:
     """faiss.Kmeans(d, k, niter=, verbose=, gpu=) for the reference's use (cluster_creator.py:42-48).
 
@@ -415,20 +536,98 @@ class Kmeans:
         self.centroids_device = None   # [k, d] device tensor after train(); `.centroids` is its numpy copy (lazy)
         self._centroids_host = None
         self._iteration_stats, self._stats_pending = [], None
+        self._last_assign = None            # ids of the last iteration's search (this rank's training rows)
+        self._perm_cache = OrderedDict()    # _subsample_perm
+        self._cperm_cache = None            # ((k, d), the grouping the last pruned train() ended with)
+        self._grouping_of_result = None     # that grouping, until _finish has remembered it for the result
         self.index = None
         self.phase_seconds = None
         self.prune = True  # exact pruning of Lloyd iterations 2..niter (d = 64 / 128 only)
         self.order_beside = True   # the visiting-order sort on a stream of its own (A/B aid)
-        self.exchange = "auto"     # "gather" | "scatter" | "auto": how the per-iteration partials are combined (see train)
+        self.exchange = "auto"     # "gather" | "scatter" | "auto": how the per-iteration partials are combined (see _exchange)
 
     # ------------------------------------------------------------------------------------
     def train(self, x, init_centroids=None, sync=True, check_finite=True):
         """-> final objective (float), like faiss.  sync=False returns None without waiting for the device:
         centroids_device is valid in stream order, `.centroids` / `.obj` / `.iteration_stats` wait when read.
         check_finite=False skips faiss' NaN/Inf scan of x (a host round trip) for callers that have made it."""
-        be = self.backend
-        k, d = self.k, self.d
+        be, k, d, niter, spherical = self.backend, self.k, self.d, self.niter, self.spherical
         dist = _Dist(self._dist_enabled, self._group)
+        ts = self._training_set(x, dist, check_finite)
+        xs, ns = ts.xs, ts.ns
+        self._stats_pending = None
+        self._iteration_stats = []
+        if ns == k:  # faiss corner case: the training set becomes the centroids
+            cent = ts.rows_at(np.arange(k))
+            self._iteration_stats.append(dict(obj=0.0, time=0.0, time_search=0.0, imbalance_factor=1.0, nsplit=0))
+            return self._finish(cent, sync)
+
+        if init_centroids is not None:
+            cent = be._f32(init_centroids).clone()
+            assert tuple(cent.shape) == (k, d), f"init_centroids must be [{k}, {d}]"
+        else:
+            cent = ts.rows_at(be.rand_perm_prefix(ns, self.seed + 1, k))
+        if spherical:
+            cent = be.renorm_rows(cent)
+
+        # ---- Lloyd iterations -------------------------------------------------------------
+        # Nothing below waits for the device: empty clusters are repaired by a device kernel (same draws, same
+        # bits as faiss' host loop) and {objective, imbalance, nsplit} of every iteration stay in two small device
+        # arrays that are read once, after the last iteration (or per iteration when verbose).
+        stats_dev = be.zeros((max(niter, 1), 2), torch.float64)
+        nsplit_dev = be.zeros((max(niter, 1),), torch.int32)
+        t0 = time.time()
+        prof = self.phase_seconds  # None, or a dict that collects per-phase wall time (debug aid)
+
+        def lap(name, t_prev):
+            if prof is None:
+                return t_prev
+            be.synchronize()
+            now = time.perf_counter()
+            prof[name] = prof.get(name, 0.0) + (now - t_prev)
+            return now
+
+        # Iterations after the first reuse the previous assignment as a guess.  With d = 64/128 the
+        # sweep is also pruned (exact: see csrc/prune.hip): `sweep` is that path's state, None without it.
+        sweep = self._pruned_sweep(xs, cent, init_centroids)
+        ids = dis = order = vorder = None
+        for it in range(niter):
+            tp = time.perf_counter()
+            if sweep is not None:
+                ids, dis = sweep.search(it, xs, cent, vorder)
+            elif spherical:   # one dense inner-product sweep per iteration; `dis` holds the products
+                ids, dis = be.assign_ip(xs, cent)
+            elif ids is None:
+                ids, dis = be.assign(xs, cent)
+            else:  # same answer, guided by the previous assignment and its member-list order
+                ids, dis = be.assign_hinted(xs, cent, ids, order)
+            tp = lap("assign", tp)
+            part, order, vorder = self._accumulate(xs, ids, dis, pruned=sweep is not None, last=it + 1 == niter)
+            tp = lap("accumulate", tp)
+            parts, objs = self._exchange(dist, part)
+            cent, hassign = be.centroid_finalize(parts, k, d)
+            # statistics + repair of empty clusters (HipBackend: two single-workgroup passes, one launch)
+            be.lloyd_stats_split(hassign, cent, ns, nsplit_dev[it:it + 1], parts, stats_dev[it], objs=objs)
+            if spherical:
+                cent = be.renorm_rows(cent)
+            tp = lap("exchange+finalize+split", tp)
+            if sweep is not None:
+                sweep.iteration_queued()
+        self._last_assign = ids
+        self._stats_pending = (stats_dev[:niter], nsplit_dev[:niter], t0)
+        if self.verbose:   # faiss' per-iteration lines, printed once the iterations are through (no wait inside the loop)
+            for it, st in enumerate(self.iteration_stats):
+                print(f"  Iteration {it} ({st['time']:.2f} s, search {st['time_search']:.2f} s): "
+                      f"objective={st['obj']:g} imbalance={st['imbalance_factor']:.3f} nsplit={st['nsplit']}", flush=True)
+        if sweep is not None:
+            self._grouping_of_result = sweep.final_grouping()
+            self._cperm_cache = ((k, d), self._grouping_of_result)
+        return self._finish(cent, sync)
+
+    # -- the pieces of train() ----------------------------------------------------------------
+    def _training_set(self, x, dist, check_finite) -> _TrainingSet:
+        """faiss' input checks and subsample_training_set on this rank's rows `x`."""
+        be, k, d = self.backend, self.k, self.d
         if isinstance(x, np.ndarray):
             assert x.flags.c_contiguous, "x must be C-contiguous"  # faiss asserts the same
         x = be._f32(x)
@@ -443,240 +642,90 @@ class Kmeans:
         if check_finite and dist.any_flag(be.any_nonfinite(x) if n_loc else False, be.device):
             raise RuntimeError("Error: 'std::isfinite(x_in[i])' failed: input contains NaN's or Inf's")
 
-        # ---- subsample_training_set -------------------------------------------------------
         if n > k * self.max_points_per_centroid:
             ns = k * self.max_points_per_centroid
             if self.verbose:
                 print(f"Sampling a subset of {ns} / {n} for training")
             perm = self._subsample_perm(n, ns)      # device int32 [ns]: faiss' rand_perm(n, seed)[:ns]
-            if dist.on:
-                mine = (perm >= off) & (perm < off + n_loc)
-                pos = torch.nonzero(mine).reshape(-1)              # subsample positions this rank owns (ascending)
-                xs = be.gather_rows(x, (perm[mine] - off).to(torch.int32).contiguous())
-            else:
-                pos = None
-                xs = be.gather_rows(x, perm)
-        else:
-            ns = n
-            if ns < k * self.min_points_per_centroid:
-                print(f"WARNING clustering {ns} points to {k} centroids: please provide at least "
-                      f"{k * self.min_points_per_centroid} training points", file=sys.stderr)
-            xs = x
-            pos = off + torch.arange(n_loc, dtype=torch.int64, device=x.device) if dist.on else None
-
-        def rows_at(positions):
-            """Rows of the (global) subsample at `positions` [m] -> device [m, d], on every rank."""
-            positions = np.asarray(positions, dtype=np.int64)
             if not dist.on:
-                return be.gather_rows(xs, positions.astype(np.int32))
-            out = be.zeros((len(positions), d))
-            want = be.from_host(positions)
-            if pos.numel():
-                j = torch.searchsorted(pos, want).clamp_(max=pos.numel() - 1)
-                ok = pos[j] == want
-                if bool(ok.any()):
-                    out[ok] = be.gather_rows(xs, j[ok].to(torch.int32).contiguous())
-            return dist.sum_bits(out)
+                return _TrainingSet(be, dist, be.gather_rows(x, perm), ns, None)
+            mine = (perm >= off) & (perm < off + n_loc)
+            pos = torch.nonzero(mine).reshape(-1)              # subsample positions this rank owns (ascending)
+            return _TrainingSet(be, dist, be.gather_rows(x, (perm[mine] - off).to(torch.int32).contiguous()), ns, pos)
+        if n < k * self.min_points_per_centroid:
+            print(f"WARNING clustering {n} points to {k} centroids: please provide at least "
+                  f"{k * self.min_points_per_centroid} training points", file=sys.stderr)
+        pos = off + torch.arange(n_loc, dtype=torch.int64, device=x.device) if dist.on else None
+        return _TrainingSet(be, dist, x, n, pos)
 
-        self._stats_pending = None
-        self._iteration_stats = []
-        if ns == k:  # faiss corner case: the training set becomes the centroids
-            cent = rows_at(np.arange(k))
-            self._iteration_stats.append(dict(obj=0.0, time=0.0, time_search=0.0, imbalance_factor=1.0, nsplit=0))
-            return self._finish(cent, sync)
+    def _pruned_sweep(self, xs, cent, init_centroids):
+        """The state of the exact pruned sweep over this train(), or None where the sweep is off or does not apply."""
+        k, d = self.k, self.d
+        if not (self.prune and not self.spherical and _PrunedSweep.applies(self.backend, d, k, xs.shape[0])):
+            return None
+        cached = self._cperm_cache
+        if init_centroids is None or cached is None or cached[0] != (k, d):
+            return _PrunedSweep(self.backend, k, self.niter, cent, cold=init_centroids is None)
+        own_result = init_centroids is self.centroids_device or init_centroids is self._centroids_host
+        return _PrunedSweep(self.backend, k, self.niter, cent, cold=False, begin_with=cached[1], regroup=not own_result)
 
-        if init_centroids is not None:
-            cent = be._f32(init_centroids).clone()
-            assert tuple(cent.shape) == (k, d), f"init_centroids must be [{k}, {d}]"
+    def _accumulate(self, xs, ids, dis, pruned, last):
+        """Queues this rank's packed partial of one iteration (HostHelpers.part_layout: centroid sums, counts and the
+        objective sum_i dis[i]) and the row order the next search wants -> (part, order, vorder): `order` is the
+        member-list order assign_hinted takes, `vorder` the visiting order of the pruned sweep; the other is None."""
+        be, k = self.backend, self.k
+        obj_off, part_len = be.part_layout(k, self.d)
+        part = be.empty((part_len,))
+        obj_view = part[obj_off:obj_off + 2].view(torch.float64)             # this rank's objective rides along
+        if not pruned:
+            be.sum_f64(dis, out=obj_view)
+            part, order = be.centroid_accum(xs, ids, k, out=part, want_order=True)
+            return part, order, None
+        # The next iteration's visiting order depends on this assignment only: its sort runs behind the short-list
+        # accumulation while the long lists are still being summed on the side stream (defer_join).
+        if xs.shape[0] >= 96 * k and self.order_beside and not last:
+            # a third stream, beside both accumulations: the visiting order of the next iteration and the objective
+            vjoin = be.visit_order_beside(ids, dis, k, sum_out=obj_view)
+            be.centroid_accum(xs, ids, k, out=part, defer_join=True)
+            vorder = vjoin()
+            be.centroid_accum_join()
+            return part, None, vorder
+        sjoin = be.sum_beside(dis, obj_view)      # beside the accumulation; joined before the partial is used
+        if xs.shape[0] < 96 * k:
+            # With few rows per cluster on this rank (sharded runs) a cluster fills a tile or two and sorting its
+            # rows by distance buys nothing: the member-list order of the accumulation doubles as the visiting
+            # order and the second sort of the iteration is dropped (measured: -8 % per iteration at 32 rows per cluster).
+            part, vorder = be.centroid_accum(xs, ids, k, out=part, want_order=True, defer_join=True)
         else:
-            cent = rows_at(be.rand_perm_prefix(ns, self.seed + 1, k))
-        spherical = self.spherical
-        if spherical:
-            cent = be.renorm_rows(cent)
+            be.centroid_accum(xs, ids, k, out=part, defer_join=True)
+            vorder = be.visit_order(ids, dis, k) if not last else None
+        be.centroid_accum_join()
+        sjoin()
+        return part, None, vorder
 
-        # ---- Lloyd iterations -------------------------------------------------------------
-        # Nothing below waits for the device: empty clusters are repaired by a device kernel (same draws, same
-        # bits as faiss' host loop) and {objective, imbalance, nsplit} of every iteration stay in two small device
-        # arrays that are read once, after the last iteration (or per iteration when verbose).
-        niter = self.niter
-        stats_dev = be.zeros((max(niter, 1), 2), torch.float64)
-        nsplit_dev = be.zeros((max(niter, 1),), torch.int32)
-        obj_off, part_len = be.part_layout(k, d)
-        # the exchange: an all-gather of whole partials (one collective, (N-1) x the table per rank) up to 4 MB,
-        # all-to-all + ordered local sum + all-gather (2 (N-1)/N x the table) above; both add in rank order
-        scatter_exchange = dist.on and (self.exchange == "scatter" or (self.exchange == "auto" and part_len * 4 > (4 << 20)))
-        t0 = time.time()
-        prof = self.phase_seconds  # None, or a dict that collects per-phase wall time (debug aid)
-
-        def lap(name, t_prev):
-            if prof is None:
-                return t_prev
-            be.synchronize()
-            now = time.perf_counter()
-            prof[name] = prof.get(name, 0.0) + (now - t_prev)
-            return now
-
-        # Iterations after the first reuse the previous assignment as a guess.  With d = 64/128 the
-        # sweep is also pruned (exact: see csrc/prune.hip); the spatial grouping of the centroids it
-        # relies on is computed once per train() -- it only affects how much gets skipped.
-        prune = (self.prune and not spherical and hasattr(be, "assign_pruned") and d in (64, 128) and k >= 1024
-                 and (k + 31) // 32 <= 512 and xs.shape[0] >= 4096)
-        ids = dis = order = vorder = None
-        # With few rows per cluster on this rank (sharded runs) a cluster fills a tile or two and sorting its
-        # rows by distance buys nothing: the member-list order of the accumulation doubles as the visiting
-        # order and the second sort of the iteration is dropped.
-        member_order = prune and xs.shape[0] < 96 * k   # (measured: -8 % per iteration at 32 rows per cluster)
-        regrouping = None   # host grouping of newer centroids, under way on the helper thread
-        regrouping_is_late = False
-
-        def regroup_beside(c):
-            """Host grouping of the centroids `c` on the helper thread; the copy to the host is queued on the
-            stream and waited for there, not here."""
-            h, ready = be.to_host_async(c)
-
-            def job():
-                ready.synchronize()
-                return be.group_rows_kd(h.numpy())
-            return _grouper().submit(job)
-
-        if prune:
-            # The spatial grouping only decides how much the exact sweep can skip.  A warm start begins with
-            # the grouping the previous train() ended with while the host regroups the new initial centroids
-            # beside the first iterations; a cold start groups its initial centroids before it can begin.
-            upload = getattr(be, "from_host_async", be.from_host)   # (the small table goes up without draining the stream)
-            cached = getattr(self, "_cperm_cache", None)
-            if init_centroids is not None and cached is not None and cached[0] == (k, d):
-                cperm = cached[1]
-                # (continuing from this object's own result: that grouping is of centroids a few iterations
-                # older than these, nothing to redo)
-                if not (init_centroids is getattr(self, "centroids_device", None)
-                        or init_centroids is self.__dict__.get("_centroids_host")):
-                    regrouping = regroup_beside(cent)
-            else:
-                cperm = be.from_host(be.group_rows_kd(be.to_host(cent)))
-            gnbr = None
-        # a last regrouping near the end: the next warm start and the tokeniser's index begin with it
-        late_regroup = niter - 6 if niter >= 10 else -1
-        # The host queues an iteration several times faster than the device runs it.  Left alone it would be a whole
-        # training ahead, and a regrouping -- which needs the device to have reached the centroids it groups, plus
-        # ~3 ms of host work -- would arrive after the host had queued every iteration that could have used it.  So
-        # the host stays at most three iterations ahead (waiting on an event three iterations old: the device always
-        # has queued work), measures the device's iteration time from those events, and submits the late regrouping
-        # early enough to be finished when the last iteration is (short iterations: a shard of an N-GPU run).
-        paced = collections.deque()
-        iter_ms = None
-        last_done = None
-        timed_events = hasattr(be, "record_event_timed")
-
-        def late_due(it):
-            if late_regroup < 0 or it < niter // 2:
-                return False
-            return it >= late_regroup or (iter_ms is not None and (niter - it) * iter_ms <= 4.5)
-
-        def pruned_assign(it):
-            """Queues iteration `it`'s exact search over the current centroids -> (ids, dis)."""
-            nonlocal cperm, regrouping, regrouping_is_late, gnbr
-            if regrouping is not None and regrouping.done():
-                cperm = upload(regrouping.result())
-                regrouping = None
-            elif (it == 2 and init_centroids is None and regrouping is None) or (late_due(it) and not regrouping_is_late):
-                # cold start: regroup once the centroids have settled (taken up when the host is done); near the end:
-                # for the next warm start and the tokeniser (replaces one still under way: these centroids are newer)
-                regrouping_is_late = late_due(it)
-                regrouping = regroup_beside(cent)
-            dmin = be.group_min_dist(cent, cperm)
-            if ids is None:   # no previous assignment yet: coarse-to-fine exact search
-                gnbr = be.group_neighbours(be.group_means(cent, cperm), 8)
-                return be.assign_c2f(xs, cent, cperm, dmin, gnbr)
-            return be.assign_pruned(xs, cent, vorder if vorder is not None else be.visit_order(ids, dis, k),
-                                    cperm, dmin, image_current=True)
-
-        for it in range(niter):
-            tp = time.perf_counter()
-            if prune:
-                ids, dis = pruned_assign(it)
-            elif spherical:   # one dense inner-product sweep per iteration; `dis` holds the products
-                ids, dis = be.assign_ip(xs, cent)
-            elif ids is None:
-                ids, dis = be.assign(xs, cent)
-            else:  # same answer, guided by the previous assignment and its member-list order
-                ids, dis = be.assign_hinted(xs, cent, ids, order)
-            tp = lap("assign", tp)
-            part = be.empty((part_len,))
-            obj_view = part[obj_off:obj_off + 2].view(torch.float64)             # this rank's objective rides along
-            beside = prune and not member_order and self.order_beside and it + 1 < niter
-            sjoin = None
-            if not beside:
-                if prune and hasattr(be, "sum_beside"):
-                    sjoin = be.sum_beside(dis, obj_view)      # beside the accumulation; joined before the partial is used
-                else:
-                    be.sum_f64(dis, out=obj_view)
-            if prune:
-                # the next iteration's visiting order depends on this assignment only: its sort runs behind
-                # the short-list accumulation while the long lists are still being summed on the side stream
-                if member_order:
-                    part, vorder = be.centroid_accum(xs, ids, k, out=part, want_order=True, defer_join=True)
-                elif beside:
-                    # a third stream, beside both accumulations: the visiting order of the next iteration and the objective
-                    vjoin = be.visit_order_beside(ids, dis, k, sum_out=obj_view)
-                    be.centroid_accum(xs, ids, k, out=part, defer_join=True)
-                    vorder = vjoin()
-                else:
-                    be.centroid_accum(xs, ids, k, out=part, defer_join=True)
-                    vorder = be.visit_order(ids, dis, k) if it + 1 < niter else None
-                be.centroid_accum_join()
-                if sjoin is not None:
-                    sjoin()
-            else:
-                part, order = be.centroid_accum(xs, ids, k, out=part, want_order=True)
-            tp = lap("accumulate", tp)
-            if scatter_exchange:
-                # (N-1)/N of the partial out, the reduced table back: sums and counts added in rank order by
-                # at_sum_parts_f32 on the slice each rank owns; the objectives travel as N doubles
-                red = be.empty((1, part_len))
-                red[0, :obj_off] = dist.reduce_in_rank_order(be, part[:obj_off])
-                red[0, obj_off:] = 0.0
-                objs = dist.all_gather_f64(part[obj_off:obj_off + 2].view(torch.float64))
-                cent, hassign = be.centroid_finalize(red, k, d)
-                parts, objs = red, objs.contiguous()
-            else:
-                parts, objs = dist.all_gather_parts(part), None
-                cent, hassign = be.centroid_finalize(parts, k, d)
-            if hasattr(be, "lloyd_stats_split"):    # statistics + repair of empty clusters: two single-workgroup passes, one launch
-                be.lloyd_stats_split(hassign, cent, ns, nsplit_dev[it:it + 1], parts, stats_dev[it], objs=objs)
-            else:
-                be.lloyd_stats(hassign, parts, k, d, stats_dev[it], objs=objs)
-                be.split_clusters_device(hassign, cent, ns, nsplit_dev[it:it + 1])
-            if spherical:
-                cent = be.renorm_rows(cent)
-            tp = lap("exchange+finalize+split", tp)
-            if prune and timed_events:
-                paced.append(be.record_event_timed())
-                if len(paced) > 3:
-                    done = paced.popleft()
-                    done.synchronize()
-                    if last_done is not None:
-                        iter_ms = last_done.elapsed_time(done)
-                    last_done = done
-        self._last_assign = ids
-        self._stats_pending = (stats_dev[:niter], nsplit_dev[:niter], t0)
-        if self.verbose:   # faiss' per-iteration lines, printed once the iterations are through (no wait inside the loop)
-            for it, st in enumerate(self.iteration_stats):
-                print(f"  Iteration {it} ({st['time']:.2f} s, search {st['time_search']:.2f} s): "
-                      f"objective={st['obj']:g} imbalance={st['imbalance_factor']:.3f} nsplit={st['nsplit']}", flush=True)
-        if prune:
-            if regrouping is not None and (regrouping.done() or regrouping_is_late):
-                cperm = upload(regrouping.result())     # (submitted early enough to be done, or about to be)
-            self._cperm_cache = ((k, d), cperm)
-            self._grouping_of_result = cperm
-        return self._finish(cent, sync)
+    def _exchange(self, dist, part):
+        """This rank's packed partial -> (parts, objs) for centroid_finalize and lloyd_stats_split, both of which add
+        in rank order.  Up to 4 MB: an all-gather of whole partials (one collective, (N-1) x the table per rank), the
+        objectives riding along (objs None).  Above: all-to-all + ordered local sum + all-gather (2 (N-1)/N x the
+        table) -- (N-1)/N of the partial out, the reduced table back, sums and counts added by at_sum_parts_f32 on the
+        slice each rank owns -- and the objectives travel as N doubles."""
+        be = self.backend
+        obj_off, part_len = be.part_layout(self.k, self.d)
+        scatter = dist.on and (self.exchange == "scatter" or (self.exchange == "auto" and part_len * 4 > (4 << 20)))
+        if not scatter:
+            return dist.all_gather_parts(part), None
+        red = be.empty((1, part_len))
+        red[0, :obj_off] = dist.reduce_in_rank_order(be, part[:obj_off])
+        red[0, obj_off:] = 0.0
+        objs = dist.all_gather_f64(part[obj_off:obj_off + 2].view(torch.float64))
+        return red, objs.contiguous()
 
     # -- results ----------------------------------------------------------------------------
     def _subsample_perm(self, n, m):
         """faiss' rand_perm(n, seed)[:m] on the device.  A pure function of (n, seed, m); the file batches of one
         run (one Kmeans object, as in ClusterCreator.run) mostly share n, so the last two are kept."""
         key = (int(n), self.seed, int(m))
-        cache = self.__dict__.setdefault("_perm_cache", OrderedDict())
+        cache = self._perm_cache
         hit = cache.get(key)
         if hit is None:
             hit = cache[key] = self.backend.rand_perm_prefix_device(n, self.seed, m)
@@ -684,7 +733,15 @@ class Kmeans:
                 cache.popitem(last=False)
         return hit
 
-    def _read_stats(self, stats_dev, nsplit_dev, t0):
+    def queued_stats(self):
+        """The statistics of the last train() while they are still on the device (None once they have been read, or if
+        there are none): a handle for read_stats(), good beyond later train() calls (sync=False callers that train
+        batch after batch and read everything at the end)."""
+        return self._stats_pending
+
+    def read_stats(self, handle):
+        """queued_stats() handle -> that training's iteration_stats (waits for it)."""
+        stats_dev, nsplit_dev, t0 = handle
         be = self.backend
         st, ns = be.to_host(stats_dev), be.to_host(nsplit_dev)     # (waits for the iterations queued so far)
         if (ns < 0).any():
@@ -698,7 +755,7 @@ class Kmeans:
         """faiss' ClusteringIterationStats of the last train() (read back from the device on first use; `time`
         and `time_search` are the elapsed time spread evenly, the iterations are not timed one by one)."""
         if self._stats_pending is not None:
-            self._iteration_stats = self._read_stats(*self._stats_pending)
+            self._iteration_stats = self.read_stats(self._stats_pending)
             self._stats_pending = None
         return self._iteration_stats
 
@@ -717,9 +774,9 @@ class Kmeans:
         """Offers the spatial grouping this object ended with to an IndexFlatL2 later filled with `table`
         (e.g. the normalised centroids a tokeniser loads): nearby rows stay nearby, and the grouping only
         ever decides how much the exact search skips."""
-        cached = getattr(self, "_cperm_cache", None)
-        be = self.backend
-        if cached is not None and hasattr(be, "remember_grouping"):
+        cached = self._cperm_cache
+        if cached is not None:
+            be = self.backend
             table = be.to_host(table) if isinstance(table, torch.Tensor) else np.asarray(table)
             if table.shape == cached[0]:
                 be.remember_grouping(table, cached[1])
@@ -729,11 +786,10 @@ class Kmeans:
         self._centroids_host = None
         self.index = (IndexFlatIP if self.spherical else IndexFlatL2)(self.d, backend=self.backend)
         self.index.add(cent)
-        be = self.backend
-        if getattr(self, "_grouping_of_result", None) is not None and hasattr(be, "remember_grouping"):
+        if self._grouping_of_result is not None:
             # for the index a tokeniser later builds from these very centroids (needs their host copy: sync)
             if sync:
-                be.remember_grouping(self.centroids, self._grouping_of_result)
+                self.backend.remember_grouping(self.centroids, self._grouping_of_result)
             self._grouping_of_result = None
         if not sync:
             return None
@@ -796,7 +852,7 @@ class IndexFlatL2:
                 and (k + 31) // 32 <= 512 and x.shape[0] >= 65536):
             if self._prune is None:
                 c_host = be.to_host(c)
-                cperm = be.recall_grouping(c_host) if hasattr(be, "recall_grouping") else None
+                cperm = be.recall_grouping(c_host)
                 if cperm is None or cperm.numel() != ((k + 31) // 32) * 32:
                     cperm = be.from_host(be.group_rows_kd(c_host))
                 # 4 neighbour groups for the one-launch guess generator (measured: 1-4 equal, 8 is 6 % slower)

@@ -195,7 +195,7 @@ class DevicePipeline:
             # (no host round trip inside: the frames were scanned for NaN/Inf once, above; the statistics of
             # every batch are read back after the last one)
             km.train(x, init_centroids=None if b == 0 else km.centroids_device, sync=False, check_finite=False)
-            pending.append(km._stats_pending)
+            pending.append(km.queued_stats())
         centroids = be.l2norm_rows(km.centroids_device)
         km.lend_grouping(centroids)
         sync(); secs["kmeans"] = time.perf_counter() - t0
@@ -225,7 +225,7 @@ class DevicePipeline:
             # the verdict is confirmed by the scan it replaced (an error path: never on the timed one)
             if not take_flag or over_ranks(be.nonfinite_flag(frames_tr)):
                 raise RuntimeError("Error: 'std::isfinite(x_in[i])' failed: input contains NaN's or Inf's")
-        stats = [km._read_stats(*p) for p in pending if p is not None]
+        stats = [km.read_stats(p) for p in pending if p is not None]
         return PipelineResult(centroids, tok_tr, tok_va, T, secs, stats)
 
     # -- host-resident inputs ------------------------------------------------------------------
