@@ -97,6 +97,8 @@ SIGNATURES = {
     "at_prune_mask_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp]),
     "at_gather_rows_f32": (_i32, [_vp, _vp, _i32, _vp, _i64, _vp, _vp]),
     "at_centroid_accum_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "at_centroid_accum_weighted_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "at_waccum_limits": (_i32, [_c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i32)]),
     "at_centroid_finalize_f32": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "at_split_clusters_f32": (_i32, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
     "at_lloyd_stats_f64": (_i32, [_vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp]),

@@ -1086,6 +1086,34 @@ class HipBackend(HostHelpers):
                 self.lib.at_centroid_accum_defer(self.ctx.handle, 0)
         return (out, (order, sorted_ids)) if want_order else out
 
+    def centroid_accum_weighted(self, x, w, ids, k, out=None, want_order=False):
+        """centroid_accum with a weight per row (at_centroid_accum_weighted_f32): the packed partial holds, per cluster
+        and in ascending row order, the chains fmaf(x[i], w[i], .) where centroid_accum has the sums and w[i] + . where
+        it has the counts.  Everything runs on the current stream: there is nothing to defer or join.  want_order as
+        in centroid_accum."""
+        x = self._f32(x)
+        n, d = x.shape
+        w = self._f32(w)
+        assert w.dim() == 1 and w.numel() == n, f"weights must be [{n}]"
+        assert ids.dtype == torch.int64 and ids.is_contiguous() and ids.numel() == n
+        if out is None:
+            out = self.empty((k * d + k,))
+        order = self.empty((n,), torch.int32) if want_order else None
+        sorted_ids = self.empty((n,), torch.int32) if want_order else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_centroid_accum_weighted_f32(
+                self.ctx.handle, _ptr(x), _ptr(w), n, d, _ptr(ids), k, _ptr(out), _vp(out.data_ptr() + 4 * k * d),
+                _ptr(order), _ptr(sorted_ids), self._stream()))
+        return (out, (order, sorted_ids)) if want_order else out
+
+    @staticmethod
+    def waccum_limits() -> dict:
+        """include/at_debug.h, at_waccum_limits: the member-list lengths at which the weighted accumulation changes its
+        path (for the tests that pin them)."""
+        v = [ctypes.c_int(0) for _ in range(4)]
+        _lib.check(_lib.load().at_waccum_limits(*[ctypes.byref(c) for c in v]))
+        return dict(zip(("short_batch", "short_batch_wide", "long_list", "ring_chunk"), (int(c.value) for c in v)))
+
     def centroid_finalize(self, parts, k, d):
         """parts [n_parts, k*d + k] packed partials (rank order) -> (centroids [k, d], hassign [k])."""
         if parts.dim() == 1:

@@ -93,6 +93,12 @@ enum at_ws_slot {
     WS_RQ_TMP,         // at_rq_encode_f32 general path: the running residual, when the caller takes none
     WS_MFCC_MAX,       // at_mfcc_f32 with top_db: one ordered key per clip, the maximum of its log-mel values (mfcc.hip)
     WS_MFCC_DCT,       // at_mfcc_f32 without a caller's table: the table of at_dct_matrix_host for (mfcc_dct_nmfcc, mfcc_dct_nmels)
+    WS_WACC_KEYS_A,    // at_centroid_accum_weighted_f32: its own sort buffers (it never shares the unweighted accumulation's)
+    WS_WACC_KEYS_B,
+    WS_WACC_VALS_A,
+    WS_WACC_VALS_B,
+    WS_WACC_TMP,
+    WS_WACC_SEG,       // ... its k+2 segment starts and the list of its long clusters
     WS_NSLOTS
 };
 
@@ -176,6 +182,7 @@ enum at_guard_id {
     AT_GUARD_PQ,        // fused at_pq_encode_f32: WS_PQ_IMG
     AT_GUARD_RQ,        // at_rq_encode_f32: WS_RQ_IMG, WS_RQ_TMP
     AT_GUARD_MFCC,      // at_mfcc_f32 with top_db or without a caller's table: WS_MFCC_MAX, WS_MFCC_DCT
+    AT_GUARD_WACC,      // at_centroid_accum_weighted_f32: WS_WACC_*
     AT_NGUARDS
 };
 

@@ -32,7 +32,9 @@ constexpr int SPLIT_ROUND = SPLIT_BLOCKS * WG;   // candidates tested per step w
 __device__ __forceinline__ float rand_float_of(uint32_t raw) { return __uint2float_rn(raw) * 2.3283064365386963e-10f; }
 
 // stats[0] = sum over the parts (ascending) of the double at obj_parts[p * stride];
-// stats[1] = faiss imbalance_factor = k * sum(h^2) / (sum h)^2 (the sums are of integers < 2^53: exact in any order)
+// stats[1] = faiss imbalance_factor = k * sum(h^2) / (sum h)^2 (the sums are of integers < 2^53: exact in any order.
+// In a weighted training -- Kmeans.train(x, weights=w) -- h holds weight sums, the two sums round, and the value is the one
+// of this kernel's fixed order: per-thread strided partials, then the wave and workgroup trees below)
 // (one workgroup of WG threads; every thread calls it)
 __device__ void lloyd_stats_block(const float* __restrict__ hassign, int k, const double* obj_parts, long obj_stride,
                                   int n_parts, double* __restrict__ stats) {

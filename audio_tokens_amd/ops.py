@@ -379,10 +379,11 @@ class _Dist:
 
 class _TrainingSet:
     """What one Kmeans.train() iterates over: `xs`, this rank's rows of the (global) training subsample of `ns` rows,
-    and -- sharded -- `pos`, their positions in it (ascending; None in a single process)."""
+    -- sharded -- `pos`, their positions in it (ascending; None in a single process), and `ws`, the weights of the rows
+    in `xs` (device float32 [rows of xs]; None for an unweighted training)."""
 
-    def __init__(self, be, dist, xs, ns, pos):
-        self.be, self.dist, self.xs, self.ns, self.pos = be, dist, xs, ns, pos
+    def __init__(self, be, dist, xs, ns, pos, ws=None):
+        self.be, self.dist, self.xs, self.ns, self.pos, self.ws = be, dist, xs, ns, pos, ws
 
     def rows_at(self, positions):
         """Rows of the (global) subsample at `positions` [m] -> device [m, d], on every rank."""
@@ -515,6 +516,16 @@ class Kmeans:
 
     distributed=True (and torch.distributed initialised): `x` is this rank's block of the global
     row-concatenation in rank order; the result is identical on every rank.
+
+    train(x, weights=w) is faiss' weighted training (`weights` is KEYWORD-ONLY here, faiss takes it as the second
+    positional argument: an existing train(x, c) keeps its meaning).  The rows and their weights are subsampled
+    together; initial centroids, the search and the per-iteration objective (the UNWEIGHTED sum of the returned
+    distances) do not look at the weights; the centroid of a cluster is sum_i w_i x_i * (1 / sum_i w_i), both sums taken
+    in ascending row order -- s <- fmaf(x_i, w_i, s) and s <- s + w_i from +0 --, and the weight sums stand where the
+    member counts stood: in hassign, in the imbalance factor and in split_clusters, which re-seeds every cluster whose
+    weight sum is 0.  All weights 1.0 give the bits of weights=None.  Weights are in units of "one point": with a
+    weight sum of at most k the repair of an empty cluster finds no donor and the statistics raise RuntimeError.
+    It needs a backend with centroid_accum_weighted() (else NotImplementedError, at the call).
     """
 
     def __init__(self, d, k, niter=20, verbose=False, gpu=True, seed=1234, max_points_per_centroid=256,
@@ -547,13 +558,21 @@ class Kmeans:
         self.exchange = "auto"     # "gather" | "scatter" | "auto": how the per-iteration partials are combined (see _exchange)
 
     # ------------------------------------------------------------------------------------
-    def train(self, x, init_centroids=None, sync=True, check_finite=True):
+    def train(self, x, init_centroids=None, sync=True, check_finite=True, *, weights=None):
         """-> final objective (float), like faiss.  sync=False returns None without waiting for the device:
         centroids_device is valid in stream order, `.centroids` / `.obj` / `.iteration_stats` wait when read.
-        check_finite=False skips faiss' NaN/Inf scan of x (a host round trip) for callers that have made it."""
+        check_finite=False skips faiss' NaN/Inf scan of x (a host round trip) for callers that have made it.
+
+        weights (keyword-only): one weight per row of `x` -- [n], numpy or tensor, host or device, any float dtype,
+        converted as x is; this rank's block when distributed -- for the weighted training the class describes.  A
+        wrong length or ndim raises ValueError; with check_finite so does a NaN, infinite or negative weight (one more
+        host read), without it nothing is read and the formula is followed.  None: the unweighted training, the same
+        backend calls in the same order as before the argument existed."""
         be, k, d, niter, spherical = self.backend, self.k, self.d, self.niter, self.spherical
+        if weights is not None and not hasattr(be, "centroid_accum_weighted"):
+            raise NotImplementedError("Kmeans.train: weights need a backend with centroid_accum_weighted()")
         dist = _Dist(self._dist_enabled, self._group)
-        ts = self._training_set(x, dist, check_finite)
+        ts = self._training_set(x, dist, check_finite, weights)
         xs, ns = ts.xs, ts.ns
         self._stats_pending = None
         self._iteration_stats = []
@@ -602,7 +621,7 @@ class Kmeans:
             else:  # same answer, guided by the previous assignment and its member-list order
                 ids, dis = be.assign_hinted(xs, cent, ids, order)
             tp = lap("assign", tp)
-            part, order, vorder = self._accumulate(xs, ids, dis, pruned=sweep is not None, last=it + 1 == niter)
+            part, order, vorder = self._accumulate(xs, ids, dis, pruned=sweep is not None, last=it + 1 == niter, ws=ts.ws)
             tp = lap("accumulate", tp)
             parts, objs = self._exchange(dist, part)
             cent, hassign = be.centroid_finalize(parts, k, d)
@@ -625,14 +644,21 @@ class Kmeans:
         return self._finish(cent, sync)
 
     # -- the pieces of train() ----------------------------------------------------------------
-    def _training_set(self, x, dist, check_finite) -> _TrainingSet:
-        """faiss' input checks and subsample_training_set on this rank's rows `x`."""
+    def _training_set(self, x, dist, check_finite, weights=None) -> _TrainingSet:
+        """faiss' input checks and subsample_training_set on this rank's rows `x` (and their weights)."""
         be, k, d = self.backend, self.k, self.d
         if isinstance(x, np.ndarray):
             assert x.flags.c_contiguous, "x must be C-contiguous"  # faiss asserts the same
         x = be._f32(x)
         assert x.dim() == 2 and x.shape[1] == d, f"expected [n, {d}], got {tuple(x.shape)}"
         n_loc = x.shape[0]
+        w = None
+        if weights is not None:
+            if not isinstance(weights, (np.ndarray, torch.Tensor)):
+                weights = np.asarray(weights)
+            if weights.ndim != 1 or weights.shape[0] != n_loc:
+                raise ValueError(f"weights must be [{n_loc}], one per row of x, got {tuple(weights.shape)}")
+            w = be._f32(weights)
         sizes = dist.all_gather_sizes(n_loc, be.device)
         off = sum(sizes[:dist.rank])
         n = sum(sizes)
@@ -641,22 +667,31 @@ class Kmeans:
                                f"least as large as number of clusters ({k})")
         if check_finite and dist.any_flag(be.any_nonfinite(x) if n_loc else False, be.device):
             raise RuntimeError("Error: 'std::isfinite(x_in[i])' failed: input contains NaN's or Inf's")
+        if w is not None and check_finite:
+            # the library's own check (faiss makes none): sqrt(w) is finite exactly for the finite weights >= 0 (-0 included)
+            if dist.any_flag(be.any_nonfinite(torch.sqrt(w)) if n_loc else False, be.device):
+                raise ValueError("weights must be finite and not negative")
 
         if n > k * self.max_points_per_centroid:
             ns = k * self.max_points_per_centroid
             if self.verbose:
                 print(f"Sampling a subset of {ns} / {n} for training")
             perm = self._subsample_perm(n, ns)      # device int32 [ns]: faiss' rand_perm(n, seed)[:ns]
+
+            def gathered(rows):   # the weights follow the rows: the same positions of the same permutation
+                return None if w is None else be.gather_rows(w.reshape(-1, 1), rows).reshape(-1)
+
             if not dist.on:
-                return _TrainingSet(be, dist, be.gather_rows(x, perm), ns, None)
+                return _TrainingSet(be, dist, be.gather_rows(x, perm), ns, None, gathered(perm))
             mine = (perm >= off) & (perm < off + n_loc)
             pos = torch.nonzero(mine).reshape(-1)              # subsample positions this rank owns (ascending)
-            return _TrainingSet(be, dist, be.gather_rows(x, (perm[mine] - off).to(torch.int32).contiguous()), ns, pos)
+            rows = (perm[mine] - off).to(torch.int32).contiguous()
+            return _TrainingSet(be, dist, be.gather_rows(x, rows), ns, pos, gathered(rows))
         if n < k * self.min_points_per_centroid:
             print(f"WARNING clustering {n} points to {k} centroids: please provide at least "
                   f"{k * self.min_points_per_centroid} training points", file=sys.stderr)
         pos = off + torch.arange(n_loc, dtype=torch.int64, device=x.device) if dist.on else None
-        return _TrainingSet(be, dist, x, n, pos)
+        return _TrainingSet(be, dist, x, n, pos, w)
 
     def _pruned_sweep(self, xs, cent, init_centroids):
         """The state of the exact pruned sweep over this train(), or None where the sweep is off or does not apply."""
@@ -669,14 +704,22 @@ class Kmeans:
         own_result = init_centroids is self.centroids_device or init_centroids is self._centroids_host
         return _PrunedSweep(self.backend, k, self.niter, cent, cold=False, begin_with=cached[1], regroup=not own_result)
 
-    def _accumulate(self, xs, ids, dis, pruned, last):
+    def _accumulate(self, xs, ids, dis, pruned, last, ws=None):
         """Queues this rank's packed partial of one iteration (HostHelpers.part_layout: centroid sums, counts and the
         objective sum_i dis[i]) and the row order the next search wants -> (part, order, vorder): `order` is the
-        member-list order assign_hinted takes, `vorder` the visiting order of the pruned sweep; the other is None."""
+        member-list order assign_hinted takes, `vorder` the visiting order of the pruned sweep; the other is None.
+        ws: the rows' weights; the partial then holds the weighted sums and, in the counts' place, the weight sums."""
         be, k = self.backend, self.k
         obj_off, part_len = be.part_layout(k, self.d)
         part = be.empty((part_len,))
         obj_view = part[obj_off:obj_off + 2].view(torch.float64)             # this rank's objective rides along
+        if ws is not None:
+            # Weighted: everything on the main stream, one call behind the other (the objective stays the unweighted sum).
+            be.sum_f64(dis, out=obj_view)
+            part, order = be.centroid_accum_weighted(xs, ws, ids, k, out=part, want_order=True)
+            if not pruned:
+                return part, order, None
+            return part, None, (be.visit_order(ids, dis, k) if not last else None)
         if not pruned:
             be.sum_f64(dis, out=obj_view)
             part, order = be.centroid_accum(xs, ids, k, out=part, want_order=True)
@@ -745,7 +788,8 @@ class Kmeans:
         be = self.backend
         st, ns = be.to_host(stats_dev), be.to_host(nsplit_dev)     # (waits for the iterations queued so far)
         if (ns < 0).any():
-            raise RuntimeError("Kmeans: split_clusters found no donor (every cluster has at most one point)")
+            raise RuntimeError("Kmeans: split_clusters found no donor (every cluster has at most one point; with "
+                               "weights: their sum is at most k -- weights are in units of one point)")
         el = time.time() - t0
         return [dict(obj=float(np.float32(st[i, 0])), time=el * (i + 1) / len(ns), time_search=el * (i + 1) / len(ns),
                      imbalance_factor=float(st[i, 1]), nsplit=int(ns[i])) for i in range(len(ns))]

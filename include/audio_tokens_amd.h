@@ -26,6 +26,7 @@
  *       processors/cluster_creator.py:42-56                                at_gather_rows_f32,
  *                                                                          at_assign_f32, at_assign_hinted_f32,
  *                                                                          at_centroid_accum_f32,
+ *                                                                          at_centroid_accum_weighted_f32,
  *                                                                          at_centroid_finalize_f32,
  *                                                                          at_split_clusters_host,
  *                                                                          at_sum_f32
@@ -341,6 +342,19 @@ int at_gather_rows_f32(at_ctx* ctx, const float* x, int d, const int32_t* idx, i
 int at_centroid_accum_f32(at_ctx* ctx, const float* x, int64_t n, int d, const int64_t* ids, int k,
                           float* sums, float* counts, uint32_t* order_out_or_null,
                           uint32_t* sorted_ids_out_or_null, void* stream);
+
+/* The same with a weight per row (faiss.Kmeans.train(x, weights=w); the single-rounding form is this library's
+ * contract): for the members i0 < i1 < ... of cluster c in ASCENDING i,
+ *     sums[c][f] = the chain s <- fmaf(x[i][f], w[i], s) from +0 (one rounding per member),
+ *     wsums[c]   = the chain s <- s + w[i] from +0, in the same order.
+ * With every weight 1.0f both are the bits of at_centroid_accum_f32.  w: DEVICE float [n]; nothing about its values is
+ * checked (NaN, Inf and negative weights follow the formula).  sums [k][d], wsums [k] are overwritten; ids outside
+ * [0, k) are parked; order_out_or_null / sorted_ids_out_or_null as above.  Everything is queued on `stream` (no side
+ * stream, nothing to join); the call uses workspace slots of its own, so it may run beside at_centroid_accum_f32 on
+ * another stream of the same context, and a weighted call on another stream than the previous one waits for it. */
+int at_centroid_accum_weighted_f32(at_ctx* ctx, const float* x, const float* w, int64_t n, int d, const int64_t* ids,
+                                   int k, float* sums, float* wsums, uint32_t* order_out_or_null,
+                                   uint32_t* sorted_ids_out_or_null, void* stream);
 
 /* faiss compute_centroids, scaling half, over n_parts partial results (p = data-parallel rank):
  * part p has its sums [k][d] at sums_parts + p*sums_part_stride and its counts [k] at
