@@ -91,6 +91,7 @@ SIGNATURES = {
                                _c.POINTER(_i64), _c.POINTER(_i64), _i32]),
     "at_filter_probe_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                    _c.POINTER(_i64), _vp]),
+    "at_prune_peek": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "at_group_means_f32": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "at_group_neighbours_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "at_assign_pruned_f32": (_i32, [_vp, _vp, _vp]),   # (ctx, const at_pruned_args*, stream)

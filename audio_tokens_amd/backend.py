@@ -1034,6 +1034,15 @@ class HipBackend(HostHelpers):
                                                     _ptr(approx), ctypes.byref(listed), self._stream()))
         return ids, approx, listed.value
 
+    def prune_peek(self, n, ng):
+        """Test hook: (bd float32 [n], mask int32 [ceil(n/32), ceil(ng/32)] holding uint32 bit patterns) as the preceding
+        pre-pass over n rows and ng groups (at_prune_mask_f32, same stream) left them in the context's workspace."""
+        bd = self.empty((n,), torch.float32)
+        mask = self.empty(((n + 31) // 32, (ng + 31) // 32), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_prune_peek(self.ctx.handle, n, ng, _ptr(bd), _ptr(mask), self._stream()))
+        return bd, mask
+
     def rand_perm_prefix_device(self, n: int, seed: int, m: int) -> torch.Tensor:
         """First m entries of faiss' rand_perm(n, seed) as a device int32 tensor, computed on the device
         (no host work, no upload); same bits as HostHelpers.rand_perm_prefix."""

@@ -221,6 +221,8 @@ struct at_ctx {
     int n_lds_raised;
     at_ws_guard guard[AT_NGUARDS];
     int mfcc_dct_nmfcc, mfcc_dct_nmels;   // what WS_MFCC_DCT holds (0 = nothing)
+    int64_t prepass_n;                    // rows and groups of the last at_prune_prepass (what WS_PRUNE_BD / WS_PRUNE_MASK
+    int prepass_ng;                       // hold; 0 = nothing): at_prune_peek refuses any other size
 };
 
 // host.cpp.  enter: before the call touches the guarded slots (the event is created on first use, timing disabled; the

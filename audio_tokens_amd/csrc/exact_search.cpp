@@ -235,6 +235,25 @@ extern "C" int at_prune_mask_f32(at_ctx* ctx, const float* x, int64_t n, int d, 
     return at_prune_prepass(ctx, call, n, order, hint_sorted, mode);
 }
 
+// Test hook: what the preceding at_prune_mask_f32(n, ng) on this stream left in the workspace -- bd [n] and
+// mask [ceil(n/32)][ceil(ng/32)] -- copied to the caller's device buffers, in stream order.  n and ng must be those of
+// the last pre-pass that ran (another ng would read the masks with another stride).
+extern "C" int at_prune_peek(at_ctx* ctx, int64_t n, int ng, float* bd_out, uint32_t* mask_out, void* stream_) {
+    AT_REQUIRE(ctx && bd_out && mask_out && n > 0 && ng > 0, "at_prune_peek: bad arguments");
+    const size_t bd_bytes = sizeof(float) * (size_t)n;
+    const size_t mask_bytes = sizeof(uint32_t) * (size_t)((n + 31) / 32) * (size_t)((ng + 31) / 32);
+    AT_REQUIRE(ctx->prepass_n == n && ctx->prepass_ng == ng, "at_prune_peek: the last pre-pass had n=%lld ng=%d, not n=%lld ng=%d",
+               (long long)ctx->prepass_n, ctx->prepass_ng, (long long)n, ng);
+    AT_REQUIRE(ctx->ws[WS_PRUNE_BD] && ctx->ws[WS_PRUNE_MASK] && ctx->ws_bytes[WS_PRUNE_BD] >= bd_bytes &&
+                   ctx->ws_bytes[WS_PRUNE_MASK] >= mask_bytes,
+               "at_prune_peek: workspace smaller than the pre-pass it records");
+    AT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    AT_HIP(hipMemcpyAsync(bd_out, ctx->ws[WS_PRUNE_BD], bd_bytes, hipMemcpyDeviceToDevice, stream));
+    AT_HIP(hipMemcpyAsync(mask_out, ctx->ws[WS_PRUNE_MASK], mask_bytes, hipMemcpyDeviceToDevice, stream));
+    return AT_OK;
+}
+
 extern "C" int at_filter_stats(at_ctx* ctx, int64_t* rows, int64_t* listed, double* sweep_ms, int64_t* sweeps,
                                int64_t* tiles, int64_t* refined, int reset) {
     AT_REQUIRE(ctx && rows && listed, "at_filter_stats: bad arguments");

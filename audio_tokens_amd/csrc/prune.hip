@@ -318,6 +318,8 @@ int at_prune_prepass(at_ctx* ctx, const at_exact_call& call, int64_t n, const ui
     hipStream_t stream = call.stream;
     const long waves = (n + 63) / 64;
     const dim3 grid((unsigned)((waves + WG / 64 - 1) / (WG / 64)));
+    ctx->prepass_n = n;
+    ctx->prepass_ng = call.ng;
     if (mode == 1) {  // hint_sorted holds group ids: each tile needs just those groups (+ neighbours)
         AT_LAUNCH(group_only_mask_kernel, grid, dim3(WG), 0, stream, (long)n, hint_sorted, call.ng,
                   reinterpret_cast<const uint32_t*>(call.dmin), call.bd, call.mask, call.ngw);

@@ -33,6 +33,8 @@
  *                                 refined with the lo products (NULL skips a field).  Waits for the calls in flight.
  *   at_filter_probe_f32           stage 1 of an exact call only: approx[2i], approx[2i+1] = approximate |c|^2 - 2 x.c
  *                                 of row i's winner and its gap to the runner-up; *listed = rows it would hand on.
+ *   at_prune_peek                 test hook: bd [n] and mask [ceil(n/32)][ceil(ng/32)] as the preceding at_prune_mask_f32
+ *                                 (same n, ng, same stream) left them in the workspace, copied to DEVICE buffers.
  *   at_waccum_limits              the member-list lengths at which at_centroid_accum_weighted_f32 changes its path: rows
  *                                 per register set of the one-wave kernel (lanes with 1 or 2 features / with 4), the
  *                                 longest list that kernel walks (longer ones go to the feature-sliced kernel) and the
@@ -59,6 +61,7 @@ int at_filter_stats(at_ctx* ctx, int64_t* rows, int64_t* listed, double* sweep_m
 int at_filter_probe_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, int k,
                         const uint32_t* order, const uint32_t* hint_sorted, const int32_t* cperm, int ng,
                         const float* dmin, int64_t* ids, float* approx, int64_t* listed, void* stream);
+int at_prune_peek(at_ctx* ctx, int64_t n, int ng, float* bd_out, uint32_t* mask_out, void* stream);
 int at_waccum_limits(int* short_batch, int* short_batch_wide, int* long_list, int* ring_chunk);
 
 #ifdef __cplusplus

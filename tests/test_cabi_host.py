@@ -20,7 +20,7 @@ def test_library_exports_every_declared_symbol():
         assert found, f"no declarations parsed in {name}"
         declared |= found
     op_header = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "audio_tokens_amd.h").read_text(), flags=re.S)
-    for hook in ("at_filter_probe_f32", "at_filter_stats", "at_prune_stats", "at_debug_set"):
+    for hook in ("at_filter_probe_f32", "at_filter_stats", "at_prune_stats", "at_prune_peek", "at_debug_set"):
         assert hook not in op_header, f"{hook} belongs in at_debug.h, not in the operator surface"
     lib = ctypes.CDLL(str(_lib.LIB_PATH))
     missing = [s for s in sorted(declared) if not hasattr(lib, s)]

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from guess_ref import filter_eps as _filter_eps
+
 pytestmark = pytest.mark.gpu
 
 
@@ -158,12 +160,6 @@ def test_assign_pruned_is_exact(be, oracle, switches, n, d, k, lds_kernel):
     assert np.array_equal(np.sort(o), np.arange(n))
     assert np.array_equal(hs.cpu().numpy().view(np.uint32), ids_o[o].astype(np.uint32))
     assert (np.diff(ids_o[o]) >= 0).all()
-
-
-def _filter_eps(d, H):
-    """The a-priori bound of csrc/filter.hip on |P16 + |x|^2 - true squared distance| (header there)."""
-    u, q, m = 2.0 ** -24, np.sqrt(d) * 2.0 ** -25, 3.0 * d / 16.0
-    return H * (34 * m * u * 1.01 + 3 * 2.0 ** -22 + d * u * 1.01 + 2 * u + 2 * q) + 4 * q
 
 
 @pytest.mark.parametrize("scale_x,scale_c,d", [(1.0, 1.0, 64), (30.0, 0.02, 64), (0.003, 7.0, 64), (1000.0, 1000.0, 64),
