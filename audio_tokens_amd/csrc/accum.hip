@@ -7,133 +7,20 @@
 // row is one coalesced 4d-byte read and the adds are sequential per (cluster, feature) exactly as
 // on the CPU.  No float atomics anywhere: results are bitwise reproducible.
 //
-// The kernels come first, the host driver that queues them (one plan, two ways to build the member
-// lists, one exit) is at the end of the file; DESIGN.md, "Host driver of the centroid sums", maps
-// its stages to streams.
+// The kernels that sum (and the sort keys and segment starts) are in accum_kernels.h, shared with the
+// weighted sums of waccum.hip; this file instantiates their WEIGHTED = false forms.  Here: the kernels
+// that build member lists ahead of or without the sort, then the host driver that queues everything
+// (one plan, two ways to build the member lists, one exit); DESIGN.md, "Host driver of the centroid
+// sums", maps its stages to streams.
 #include <cstdlib>
 #include <cstring>
 
+#include "accum_kernels.h"
 #include "at_internal.h"
 #include "at_sort.h"
 
 namespace {
 
-constexpr int WG = 256;
-
-__global__ void __launch_bounds__(WG) make_keys_kernel(const long* __restrict__ ids, long n, int k,
-                                                       uint32_t* __restrict__ keys,
-                                                       uint32_t* __restrict__ vals) {
-    const long i = (long)blockIdx.x * WG + threadIdx.x;
-    if (i >= n) return;
-    long c = ids[i];
-    // an id outside [0, k) (e.g. -1 from an all-NaN row) is parked in a trailing bucket that no
-    // centroid reads
-    keys[i] = (c >= 0 && c < k) ? (uint32_t)c : (uint32_t)k;
-    vals[i] = (uint32_t)i;
-}
-
-// offsets[c] = first position p in the sorted key array with keys[p] >= c, for c in [0, k].
-__global__ void __launch_bounds__(WG) segment_offsets_kernel(const uint32_t* __restrict__ keys, long n,
-                                                             int k, uint32_t* __restrict__ offsets) {
-    const int c = blockIdx.x * WG + threadIdx.x;
-    if (c > k) return;
-    long lo = 0, hi = n;
-    while (lo < hi) {
-        const long mid = (lo + hi) >> 1;
-        if (keys[mid] < (uint32_t)c) lo = mid + 1; else hi = mid;
-    }
-    offsets[c] = (uint32_t)lo;
-}
-
-// One wavefront per (cluster, 64*VEC-feature slab).  Lane owns VEC consecutive features.
-template <int VEC>
-__global__ void __launch_bounds__(WG) centroid_accum_kernel(const float* __restrict__ x, int d,
-                                                            const uint32_t* __restrict__ order,
-                                                            const uint32_t* __restrict__ offsets,
-                                                            int k, int slabs, uint32_t long_list,
-                                                            float* __restrict__ sums,
-                                                            float* __restrict__ counts) {
-    const int lane = threadIdx.x & 63;
-    const long w = (long)blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
-    if (w >= (long)k * slabs) return;
-    const int c = (int)(w / slabs);
-    const int slab = (int)(w - (long)c * slabs);
-    const int f0 = (slab * 64 + lane) * VEC;
-    const bool live = f0 < d;  // d is a multiple of VEC
-    const uint32_t beg = offsets[c], end = offsets[c + 1];
-    if (end - beg > long_list) return;  // left to centroid_accum_long_kernel
-
-    float acc[VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; v++) acc[v] = 0.0f;
-
-    // Rows are fetched RB at a time into one of two register sets: the loads of batch i+1 are in flight while
-    // batch i is added (in member order: one dependent chain per feature, as the contract says), and the member
-    // indices of the next 64 rows are fetched while this block of 64 is summed.  A list is one wave's sequential
-    // walk, so the kernel lasts as long as its longest lists (up to 2048 members): what bounds those is how many
-    // row reads the wave keeps in flight -- 16 per set (32 in flight) instead of round 2's 8: 168 -> see DESIGN us
-    // at 2 M x 64.
-    constexpr int RB = VEC == 4 ? 8 : 16;
-    auto fetch = [&](uint32_t mine, uint32_t m, uint32_t cnt, float (&t)[RB][VEC]) {
-#pragma unroll
-        for (int u = 0; u < RB; u++) {
-            const uint32_t src = __builtin_amdgcn_readlane(mine, (m + u) & 63);
-            const bool ok = (m + u < cnt) && live;
-            if constexpr (VEC == 4) {
-                float4 q = ok ? *reinterpret_cast<const float4*>(x + (size_t)src * d + f0) : make_float4(0, 0, 0, 0);
-                t[u][0] = q.x; t[u][1] = q.y; t[u][2] = q.z; t[u][3] = q.w;
-            } else if constexpr (VEC == 2) {
-                float2 q = ok ? *reinterpret_cast<const float2*>(x + (size_t)src * d + f0) : make_float2(0, 0);
-                t[u][0] = q.x; t[u][1] = q.y;
-            } else {
-                t[u][0] = ok ? x[(size_t)src * d + f0] : 0.0f;
-            }
-        }
-    };
-    auto add = [&](uint32_t m, uint32_t cnt, const float (&t)[RB][VEC]) {
-#pragma unroll
-        for (int u = 0; u < RB; u++) {
-            if (m + u < cnt) {  // wave-uniform: the tail adds nothing at all
-#pragma unroll
-                for (int v = 0; v < VEC; v++) acc[v] += t[u][v];
-            }
-        }
-    };
-    uint32_t mine_next = (beg < end && lane < min(64u, end - beg)) ? order[beg + lane] : 0u;
-    for (uint32_t base = beg; base < end; base += 64) {
-        const uint32_t cnt = min(64u, end - base);
-        const uint32_t mine = mine_next;
-        if (base + 64 < end) mine_next = lane < min(64u, end - base - 64) ? order[base + 64 + lane] : 0u;
-        float tA[RB][VEC], tB[RB][VEC];
-        fetch(mine, 0, cnt, tA);
-        for (uint32_t m = 0; m < cnt; m += 2 * RB) {
-            if (m + RB < cnt) fetch(mine, m + RB, cnt, tB);
-            add(m, cnt, tA);
-            if (m + RB < cnt) {
-                if (m + 2 * RB < cnt) fetch(mine, m + 2 * RB, cnt, tA);
-                add(m + RB, cnt, tB);
-            }
-        }
-    }
-    if (live) {
-#pragma unroll
-        for (int v = 0; v < VEC; v++) sums[(size_t)c * d + f0 + v] = acc[v];
-    }
-    if (slab == 0 && lane == 0) counts[c] = (float)(end - beg);
-}
-
-// Long member lists (one huge cluster, e.g. every digital-silence frame) would leave a single
-// wavefront chasing HBM latency for milliseconds.  The sums of different features are independent,
-// so such a cluster is cut ACROSS FEATURES: one workgroup per (long cluster, 4-feature slice).
-// Waves 1-3 stream that 16-byte slice of every member row, in member order, into a
-// double-buffered LDS ring (all index loads, then all row loads, then the LDS writes, so a whole
-// chunk is in flight at once); four lanes of wave 0 do nothing but the dependent chain of fp32
-// adds.  Same ascending-member order, hence the same bits, as the one-wave kernel.
-constexpr int LONG_CHUNK = 2048;                       // members per ring buffer (32 KiB)
-constexpr int LONG_LOADERS = WG - 64;                  // threads that load
-constexpr int LONG_PER_THREAD = (LONG_CHUNK + LONG_LOADERS - 1) / LONG_LOADERS;
-
-constexpr int EARLY_MAX = 16;       // long clusters whose member lists come from the ordered compaction
 constexpr int EARLY_ROWS = 4096;    // rows per workgroup of the ordered compaction
 
 // The three carved-up workspaces.  Each view is filled by its fetch(): the slot from at_ws, zeroed on `clear_on` when
@@ -189,117 +76,6 @@ struct EarlyLists {
         return AT_OK;
     }
 };
-
-// early != 0: list `slot` of the early lists (cluster cluster_of[slot], members early_offsets[slot] ..); marks the
-// cluster done[c] = gen.  early == 0: the regular pass over all clusters after the sort; records every long cluster
-// in pred (the next call's early set) and skips those the early pass has already summed.
-__global__ void __launch_bounds__(WG) centroid_accum_long_kernel(const float* __restrict__ x, int d,
-                                                                 const uint32_t* __restrict__ order,
-                                                                 const uint32_t* __restrict__ offsets,
-                                                                 uint32_t long_list,
-                                                                 float* __restrict__ sums,
-                                                                 float* __restrict__ counts, int k, int early,
-                                                                 const int* __restrict__ cluster_of,
-                                                                 const int* __restrict__ n_slots,
-                                                                 unsigned* __restrict__ done, unsigned gen,
-                                                                 int slot0 = 0, int slot1 = 0x7fffffff) {
-    // feature-major ring: ring[buffer][feature][member], so an adder lane reads four consecutive members of
-    // its feature with one 16-byte LDS read
-    __shared__ __attribute__((aligned(16))) float ring[2][4][LONG_CHUNK];
-    // early: slot = blockIdx.x of the early lists.  Regular pass: the workgroups stride over the late list
-    // (cluster_of[0] = its length, clusters behind it), offsets indexed by cluster.
-    const int n_slot = min(early ? min(*n_slots, EARLY_MAX) : cluster_of[0], slot1);   // (list mode: slots [slot0, slot1))
-    const int piece = blockIdx.y;  // features 4*piece .. 4*piece+3
-    for (int slot = slot0 + blockIdx.x; slot < n_slot; slot += gridDim.x) {
-    const int c = early ? cluster_of[slot] : cluster_of[1 + slot];
-    if (c < 0 || c >= k) continue;
-    const uint32_t beg = early ? offsets[slot] : offsets[c], end = early ? offsets[slot + 1] : offsets[c + 1];
-    const uint32_t len = end - beg;
-    if (len <= long_list) continue;  // uniform for the workgroup
-    const int tid = threadIdx.x;
-    const bool adder = tid < 64;
-    const uint32_t nchunks = (len + LONG_CHUNK - 1) / LONG_CHUNK;
-    const float4* rows = reinterpret_cast<const float4*>(x) + piece;
-    const int d4 = d >> 2;
-
-    auto stage = [&](uint32_t ch) {  // loaders only
-        const uint32_t m0 = ch * LONG_CHUNK;
-        const uint32_t cnt = min((uint32_t)LONG_CHUNK, len - m0);
-        const uint32_t t = tid - 64;
-        uint32_t src[LONG_PER_THREAD];
-        float4 v[LONG_PER_THREAD];
-#pragma unroll
-        for (int u = 0; u < LONG_PER_THREAD; u++) {
-            const uint32_t e = t + u * LONG_LOADERS;
-            src[u] = e < cnt ? order[beg + m0 + e] : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < LONG_PER_THREAD; u++) {
-            const uint32_t e = t + u * LONG_LOADERS;
-            v[u] = e < cnt ? rows[(size_t)src[u] * d4] : make_float4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < LONG_PER_THREAD; u++) {
-            const uint32_t e = t + u * LONG_LOADERS;
-            if (e < cnt) {
-                ring[ch & 1][0][e] = v[u].x;
-                ring[ch & 1][1][e] = v[u].y;
-                ring[ch & 1][2][e] = v[u].z;
-                ring[ch & 1][3][e] = v[u].w;
-            }
-        }
-    };
-
-    float acc = 0.0f;
-    if (!adder) stage(0);
-    __syncthreads();
-    for (uint32_t ch = 0; ch < nchunks; ch++) {
-        if (!adder) {
-            if (ch + 1 < nchunks) stage(ch + 1);
-        } else if (tid < 4) {
-            const float* src = ring[ch & 1][tid];
-            const uint32_t cnt = min((uint32_t)LONG_CHUNK, len - ch * LONG_CHUNK);
-            // one dependent chain of adds; 128 members are read per batch so that the LDS latency is paid
-            // once per 128 adds (batches of 16: 380 us on a 46 000-member list, of 128: 310 us)
-            uint32_t m = 0;
-            {
-                for (; m + 128 <= cnt; m += 128) {
-                    float4 t[32];
-#pragma unroll
-                    for (int u = 0; u < 32; u++) t[u] = *reinterpret_cast<const float4*>(src + m + 4 * u);
-#pragma unroll
-                    for (int u = 0; u < 32; u++) {
-                        acc += t[u].x;
-                        acc += t[u].y;
-                        acc += t[u].z;
-                        acc += t[u].w;
-                    }
-                }
-            }
-            for (; m + 16 <= cnt; m += 16) {
-                float4 t[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) t[u] = *reinterpret_cast<const float4*>(src + m + 4 * u);
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    acc += t[u].x;
-                    acc += t[u].y;
-                    acc += t[u].z;
-                    acc += t[u].w;
-                }
-            }
-            for (; m < cnt; m++) acc += src[m];
-        }
-        __syncthreads();
-    }
-    if (tid < 4) sums[(size_t)c * d + 4 * piece + tid] = acc;
-    if (tid == 0 && piece == 0) {
-        counts[c] = (float)len;
-        if (early && done) done[c] = gen;
-    }
-    __syncthreads();   // (the ring is reused by the next list)
-    }  // slot
-}
 
 // ---- member lists of the (predicted) long clusters, ahead of the sort -----------------------------------------
 // A list of tens of thousands of members is one dependent chain of adds, 300 us at 2 M rows: as long as everything
@@ -610,8 +386,6 @@ __global__ void __launch_bounds__(WG) segment_ids_kernel(const uint32_t* __restr
 }
 
 // ---- host driver ------------------------------------------------------------------------------------------------
-#define AT_TRY(expr) do { const int rc_ = (expr); if (rc_ != AT_OK) return rc_; } while (0)
-
 // One call: its arguments, and everything that is decided about it -- from (n, d, k, the alignment of x, the switch
 // accum_buckets) alone, before anything is queued.  Every launch below reads the plan.
 struct AccumPlan {
@@ -631,7 +405,7 @@ AccumPlan accum_plan(const at_ctx* ctx, const float* x, int64_t n, int d, const 
                      hipStream_t stream) {
     AccumPlan p{x, reinterpret_cast<const long*>(ids), (long)n, d, k, sums, counts, stream};
     const bool al = at_aligned16(x), long_ok = d % 4 == 0 && al;
-    p.long_list = long_ok ? 2048u : UINT32_MAX;
+    p.long_list = long_ok ? AccumShape<false>::LONG_LIST : UINT32_MAX;
     // The long lists are one dependent add chain per feature (the contract's summation order), a few
     // workgroups busy for as long as the longest list takes: they run on a side stream beside the
     // kernel that handles all the other clusters.
@@ -701,8 +475,8 @@ int queue_early_lists(hipStream_t ss, const AccumPlan& p, const int* pred, const
 }
 
 int launch_short_lists(const AccumPlan& p, const uint32_t* order, const uint32_t* offsets) {
-    auto* centroid_accum_kernel_vec = p.vec == 4 ? centroid_accum_kernel<4> : p.vec == 2 ? centroid_accum_kernel<2> : centroid_accum_kernel<1>;
-    AT_LAUNCH(centroid_accum_kernel_vec, dim3(p.grid), dim3(WG), 0, p.stream, p.x, p.d, order, offsets, p.k, p.slabs, p.long_list,
+    auto* centroid_accum_kernel_vec = p.vec == 4 ? centroid_accum_kernel<4, false> : p.vec == 2 ? centroid_accum_kernel<2, false> : centroid_accum_kernel<1, false>;
+    AT_LAUNCH(centroid_accum_kernel_vec, dim3(p.grid), dim3(WG), 0, p.stream, p.x, nullptr, p.d, order, offsets, p.k, p.slabs, p.long_list,
               p.sums, p.counts);
     return AT_OK;
 }
@@ -733,7 +507,7 @@ int lists_by_buckets(at_ctx* ctx, const AccumPlan& p, SideWork& side, MemberList
         AT_TRY(side.begin());   // offsets / longs are ready
         ss = ctx->side_stream;
         AT_TRY(queue_early_lists(ss, p, bt.longs + 1, bt.longs, el, order, offsets));
-        AT_LAUNCH(centroid_accum_long_kernel, dim3(EARLY_MAX, p.d / 4), dim3(WG), 0, ss, p.x, p.d, order, offsets, p.long_list,
+        AT_LAUNCH(centroid_accum_long_kernel<false>, dim3(EARLY_MAX, p.d / 4), dim3(WG), 0, ss, p.x, nullptr, p.d, order, offsets, p.long_list,
                   p.sums, p.counts, p.k, 0, bt.longs, nullptr, nullptr, 0u, 0, EARLY_MAX);
     }
     if (p.n > 0) {
@@ -746,7 +520,7 @@ int lists_by_buckets(at_ctx* ctx, const AccumPlan& p, SideWork& side, MemberList
         // more than EARLY_MAX long clusters (rare): the rest were scattered; rank-sort them, then their sums
         AT_TRY(side.begin());   // scattered segments are ready
         AT_LAUNCH(long_ranksort_kernel, dim3(16), dim3(1024), 0, ss, order, offsets, bt.longs, el.lists);
-        AT_LAUNCH(centroid_accum_long_kernel, dim3(16, p.d / 4), dim3(WG), 0, ss, p.x, p.d, order, offsets, p.long_list,
+        AT_LAUNCH(centroid_accum_long_kernel<false>, dim3(16, p.d / 4), dim3(WG), 0, ss, p.x, nullptr, p.d, order, offsets, p.long_list,
                   p.sums, p.counts, p.k, 0, bt.longs, nullptr, nullptr, 0u, EARLY_MAX, 0x7fffffff);
         AT_TRY(side.end());
     }
@@ -785,7 +559,7 @@ int lists_by_sort(at_ctx* ctx, const AccumPlan& p, SideWork& side, MemberLists* 
             AT_HIP(hipEventRecord(ctx->side_ev2, ss));
         }
         AT_TRY(queue_early_lists(ss, p, lp.pred, lp.pred_n, el, el.lists, nullptr));
-        AT_LAUNCH(centroid_accum_long_kernel, dim3(EARLY_MAX, p.d / 4), dim3(WG), 0, ss, p.x, p.d, el.lists, el.eoff, p.long_list,
+        AT_LAUNCH(centroid_accum_long_kernel<false>, dim3(EARLY_MAX, p.d / 4), dim3(WG), 0, ss, p.x, nullptr, p.d, el.lists, el.eoff, p.long_list,
                   p.sums, p.counts, p.k, 1, lp.pred, lp.pred_n, lp.done, gen, 0, 0x7fffffff);
         // the regular pass rebuilds the prediction: its counter starts from zero once the early pass has read it
         AT_HIP(hipMemsetAsync(lp.pred_n, 0, 4, ss));
@@ -803,13 +577,13 @@ int lists_by_sort(at_ctx* ctx, const AccumPlan& p, SideWork& side, MemberLists* 
     if (p.offsets_beside)
         AT_HIP(hipStreamWaitEvent(p.stream, ctx->side_ev2, 0));
     else
-        AT_LAUNCH(segment_offsets_kernel, dim3((p.k + 1 + WG - 1) / WG), dim3(WG), 0, p.stream, out->sorted_keys, p.n, p.k, offsets);
+        AT_LAUNCH(segment_offsets_kernel, dim3((p.k + 1 + WG - 1) / WG), dim3(WG), 0, p.stream, out->sorted_keys, p.n, p.k, p.long_list, offsets, nullptr);
     if (p.have_long) {
         AT_TRY(side.begin());   // sorted lists and offsets are ready
         AT_HIP(hipMemsetAsync(late, 0, 4, ss));
         AT_LAUNCH(long_detect_kernel, dim3((p.k + WG - 1) / WG), dim3(WG), 0, ss, offsets, p.k, p.long_list, lp.done, gen, lp.pred,
                   lp.pred_n, late);
-        AT_LAUNCH(centroid_accum_long_kernel, dim3(32, p.d / 4), dim3(WG), 0, ss, p.x, p.d, out->order, offsets, p.long_list,
+        AT_LAUNCH(centroid_accum_long_kernel<false>, dim3(32, p.d / 4), dim3(WG), 0, ss, p.x, nullptr, p.d, out->order, offsets, p.long_list,
                   p.sums, p.counts, p.k, 0, late, nullptr, lp.done, gen, 0, 0x7fffffff);
         AT_TRY(side.end());
     }

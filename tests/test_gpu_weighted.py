@@ -151,6 +151,21 @@ def test_unaligned_rows_give_the_same_bits(be, d):
     _verify(got, ref, K_LADDER, d, True, f"unaligned d={d}", nan_ok=True)
 
 
+@pytest.mark.parametrize("d", [4, 8])
+def test_more_long_lists_than_workgroups(be, d):
+    """66 lists of long_list + 1 members on the long-list kernel's grid of 64 workgroups per 4-feature slice (d = 4: one
+    slice, 8: two): two workgroups of a slice sum a second list each, from a ring the first one has been through."""
+    L, k = _limits()["long_list"], 70
+    lengths = [L + 1] * 66 + [3, 0, 3, 0]
+    rng = np.random.default_rng(70 + d)
+    ids, n = ids_with_lengths(lengths, rng, scatter=True)
+    assert n // (L + 1) > 64 and sum(m > L for m in lengths) > 64      # (the grid is min(n // (L + 1), 64))
+    x = rng.standard_normal((n, d)).astype(np.float32)
+    w = full_mantissa_weights(n)
+    got = be.centroid_accum_weighted(_dev(be, x), _dev(be, w), _dev(be, ids), k, out=_out(be, k, d), want_order=True)
+    _verify(got, weighted_sums(x, w, ids, k), k, d, True, f"66 long lists, d={d}")
+
+
 def test_call_forms(be):
     d = 64
     x, w, ids, ref = _ladder_case(d)
