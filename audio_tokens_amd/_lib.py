@@ -125,6 +125,8 @@ SIGNATURES = {
     "at_pq_decode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "at_rq_encode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "at_rq_decode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "at_rq_beam_step_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "at_rq_beam_encode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "at_dct_matrix_host": (_i32, [_i32, _i32, _i32, _vp]),
     "at_mfcc_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _c.c_float, _vp, _i32, _vp]),
     "at_deltas_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),

@@ -702,6 +702,47 @@ class HipBackend(HostHelpers):
                                                  _ptr(dist), _ptr(residual), _ptr(bad), self._stream()))
         return codes, dist, residual, bad
 
+    def rq_beam_step(self, r, b_in, codebook, b_out):
+        """One stage of the beam-search residual quantiser (at_rq_beam_step_f32): r [n * b_in, d] or [n, b_in, d], the
+        residuals of the b_in beams of every row, codebook [ksub, d] -> (r_out [n, b_out, d] float32, parent [n, b_out]
+        int32, code [n, b_out] uint8, dist [n, b_out] float32, bad int32 [1]): the b_out smallest of the rows'
+        b_in * min(b_out, ksub) nearest-word candidates by (distance, parent slot, word).  Nothing is read back."""
+        r, cb = self._f32(r), self._f32(codebook)
+        b_in, b_out = int(b_in), int(b_out)
+        d = cb.shape[1]
+        assert cb.dim() == 2 and r.shape[-1] == d and b_in >= 1 and r.numel() % (b_in * d) == 0, \
+            "rq_beam_step: r must hold [n, b_in, d] floats and codebook [ksub, d]"
+        n = r.numel() // (b_in * d)
+        r_out = self.empty((n, b_out, d), torch.float32)
+        parent = self.empty((n, b_out), torch.int32)
+        code = self.empty((n, b_out), torch.uint8)
+        dist = self.empty((n, b_out), torch.float32)
+        bad = self.zeros((1,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_rq_beam_step_f32(self.ctx.handle, _ptr(r), n, b_in, d, _ptr(cb), cb.shape[0], b_out,
+                                                    _ptr(r_out), _ptr(parent), _ptr(code), _ptr(dist), _ptr(bad),
+                                                    self._stream()))
+        return r_out, parent, code, dist, bad
+
+    def rq_beam_encode(self, x, codebooks, beam, want_dist=False, want_residual=False):
+        """Beam-search residual-quantiser codes (at_rq_beam_encode_f32): arguments and results as rq_encode, with a
+        beam of 1 <= beam <= 32 partial codes kept alive per row through the stages; the outputs are those of the best
+        one behind the last stage.  bad[0] is set when a slot of some stage had no candidate left.  Nothing is read back."""
+        x, cb = self._f32(x), self._f32(codebooks)
+        assert x.dim() == 2 and cb.dim() == 3, "rq_beam_encode: x must be [n, d] and codebooks [M, ksub, d]"
+        n, d = x.shape
+        M, ksub, dc = cb.shape
+        if dc != d:
+            raise ValueError(f"rq_beam_encode: codebooks {tuple(cb.shape)} do not hold rows of {d} features")
+        codes = self.empty((n, M), torch.uint8)
+        dist = self.empty((n, M), torch.float32) if want_dist else None
+        residual = self.empty((n, d), torch.float32) if want_residual else None
+        bad = self.zeros((1,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_rq_beam_encode_f32(self.ctx.handle, _ptr(x), n, d, M, ksub, _ptr(cb), int(beam),
+                                                      _ptr(codes), _ptr(dist), _ptr(residual), _ptr(bad), self._stream()))
+        return codes, dist, residual, bad
+
     def rq_decode(self, codes, codebooks):
         """codes [n, M] uint8, codebooks [M, ksub, d] -> float32 [n, d]: row codes[i, 0] of codebook 0, then the rows
         codes[i, m] of the codebooks m = 1 .. M-1 added in ascending order (at_rq_decode_f32)."""

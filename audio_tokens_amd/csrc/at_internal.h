@@ -99,6 +99,9 @@ enum at_ws_slot {
     WS_WACC_VALS_B,
     WS_WACC_TMP,
     WS_WACC_SEG,       // ... its k+2 segment starts and the list of its long clusters
+    WS_RQ_BEAM_RES,    // at_rq_beam_encode_f32: the two residual buffers [rows][B][d] of a block of rows
+    WS_RQ_BEAM_LISTS,  // at_rq_beam_step_f32 / _encode_f32: the at_knn_f32 lists of one stage (ids, then distances)
+    WS_RQ_BEAM_PATH,   // at_rq_beam_encode_f32: (parent, distance, word) of every slot of every stage of a block of rows
     WS_NSLOTS
 };
 
@@ -183,6 +186,8 @@ enum at_guard_id {
     AT_GUARD_RQ,        // at_rq_encode_f32: WS_RQ_IMG, WS_RQ_TMP
     AT_GUARD_MFCC,      // at_mfcc_f32 with top_db or without a caller's table: WS_MFCC_MAX, WS_MFCC_DCT
     AT_GUARD_WACC,      // at_centroid_accum_weighted_f32: WS_WACC_*
+    AT_GUARD_RQ_BEAM,   // at_rq_beam_step_f32 / at_rq_beam_encode_f32: WS_RQ_BEAM_* (they call at_knn_f32, which takes
+                        // AT_GUARD_KNN on the same stream inside: guards do not nest on one another's slots)
     AT_NGUARDS
 };
 

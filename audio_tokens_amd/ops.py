@@ -1113,34 +1113,49 @@ class ProductQuantizer:
 
 
 class ResidualQuantizer:
-    """Greedy residual vector quantiser (RVQ: SoundStream, EnCodec; faiss calls the family ResidualQuantizer): M
-    codebooks of ksub = 256 words of d features.  Stage 0 quantises the frame, stage m what the stages before it left
-    over; M one-byte tokens per frame, coarse to fine, every prefix of a code a valid coarser code.  Beam width 1 and one
-    plain k-means per stage: faiss's own defaults (a beam of 5, progressive-dimension training) are not implemented, and
-    the contract below is the library's own, not verified faiss output.  max_beam_size != 1 and nbits != 8 raise
-    NotImplementedError.
+    """Residual vector quantiser (RVQ: SoundStream, EnCodec; faiss calls the family ResidualQuantizer): M codebooks of
+    ksub = 256 words of d features.  Stage 0 quantises the frame, stage m what the stages before it left over; M
+    one-byte tokens per frame, coarse to fine.  max_beam_size = B, 1 <= B <= 32, keeps the B best partial codes of every
+    frame alive through the stages (B = 1: the greedy encoder, every prefix of a code a valid coarser code; faiss's own
+    default is 5).  One plain k-means per stage; the contract below is the library's own, recalled from faiss and not
+    verified against its output: faiss's look-up-table beam search, which changes the arithmetic, and its
+    progressive-dimension training are not implemented.  nbits != 8 and a max_beam_size outside 1 .. 32 raise
+    NotImplementedError, and so does max_beam_size > 1 on a backend that has neither rq_beam_step() nor knn().
 
-    train(x): r_0 = x; for m = 0 .. M-1 in order, codebook m is bit for bit the `centroids` of Kmeans(d, 256,
-    niter=niter, seed=seed, max_points_per_centroid=..., backend=backend).train(r_m), and r_{m+1} is one encode stage
-    over ALL rows of r_m (not the subsample).  Every stage uses the same seed and so the same subsample permutation;
-    codebook 0 is the plain Kmeans vocabulary.  Kmeans's errors and its small-training-set warning pass through.
+    The beam.  After stage m a row i has B_m beams, B_0 = 1 and B_{m+1} = min(B, B_m * ksub); beam s has a residual
+    R_m[i, s] (fp32), R_0[i, 0] = x[i], the codes of its path and the distance at which each ancestor was chosen.
+    Stage m: (D, I) = IndexFlatL2(d) holding codebook m asked .search(R_m.reshape(n * B_m, d), k_m) with
+    k_m = min(B_{m+1}, ksub), at_knn_f32's answer for that one call bit for bit (so the direct form is chosen by
+    n * B_m < 20; with B = 1 this is the greedy rule).  The candidates of row i are the (s, t) with I[i * B_m + s, t] >= 0;
+    the new beams are the B_{m+1} smallest by (D, s, I), lexicographic and ascending -- on equal distances the lower
+    parent slot wins, then the lower word -- slot 0 the best, and R_{m+1}[i, s'] = R_m[i, s] - codebook[m, I], one fp32
+    subtraction per feature.  A slot for which no candidate is left (only on rows with NaN, Inf or overflowing distances)
+    follows every filled slot, takes parent slot 0, code 0 and distance +inf, subtracts word 0 from parent 0's residual,
+    raises the call's flag, and is a beam like any other at the next stage.
+
+    train(x): for m = 0 .. M-1 in order, codebook m is bit for bit the `centroids` of Kmeans(d, 256, niter=niter,
+    seed=seed, max_points_per_centroid=..., backend=backend).train(R_m.reshape(n * B_m, d)) -- the residuals of all
+    beams, row-major, beam-minor -- and R_{m+1} is one beam stage over ALL rows (not the subsample).  Every stage uses
+    the same seed; codebook 0 is the plain Kmeans vocabulary.  Kmeans's errors and its small-training-set warning pass
+    through.
 
     compute_codes(x) -> uint8 [n, M] (numpy for host input, a device tensor on the caller's current stream for device
-    input).  r_0 = x; for m = 0 .. M-1: codes[i, m] is IndexFlatL2(d) holding codebook m asked .search(r_m, 1),
-    at_assign_f32's contract exactly (the direct form when the call has n < 20 rows), then
-    r_{m+1}[i] = r_m[i] - codebook[m, codes[i, m]], one fp32 subtraction per feature.  A row with no distance below +inf
-    at a stage (a NaN or Inf in it, or overflow) gets code 0 and distance +inf there and subtracts word 0; the call then
-    raises RuntimeError in faiss's words, unless check_finite=False, which returns the codes and skips the one host read.
-    return_distances=True also returns the winning distances, float32 [n, M] (column M-1 is the squared reconstruction
-    error in the expansion form), return_residual=True r_M, float32 [n, d]; the tuple is (codes, dist, residual).
+    input): the path of slot 0 behind the last stage.  The call raises RuntimeError in faiss's words when the flag is up,
+    unless check_finite=False, which returns the codes and skips the one host read.  return_distances=True also returns
+    float32 [n, M], the distance at which that path's stage-m ancestor was chosen (column M-1 is the squared
+    reconstruction error in the expansion form), return_residual=True R_M[:, 0], float32 [n, d]; the tuple is (codes,
+    dist, residual).  With B = 1: r_{m+1}[i] = r_m[i] - codebook[m, codes[i, m]] and codes[i, m] is .search(r_m, 1).
 
     decode(codes) -> float32 [n, d]: codebook[0, codes[:, 0]] copied, then + codebook[m, codes[:, m]] for m = 1 .. M-1 in
     ascending order, one fp32 addition each.  (decode(codes) + residual is not x bit for bit: fp32 addition does not
     invert the subtractions.)
 
-    A backend with rq_encode() / rq_decode() (HipBackend: csrc/rq.hip) does each call in the library, all M stages in
-    one launch at d = 64 and 128; any other backend composes one assign() per stage and a torch subtraction, and
-    decodes by indexing and adding."""
+    Routes.  B = 1: a backend with rq_encode() / rq_decode() (HipBackend: csrc/rq.hip) does each call in the library, all
+    M stages in one launch at d = 64 and 128; any other backend composes one assign() per stage and a torch subtraction,
+    and decodes by indexing and adding.  B > 1: rq_beam_encode() (HipBackend: csrc/rq_beam.hip) does the call in the
+    library; a backend with rq_beam_step() runs the stages one by one and follows the parents back in torch; a backend
+    with only knn() composes each stage from knn(), a stable torch sort on D over the (s, t) candidates in row-major
+    order (which is the (D, s, I) order, a list being in (D, I) order already), a gather and a subtraction."""
 
     def __init__(self, d, M, nbits=8, niter=25, seed=1234, max_points_per_centroid=256, max_beam_size=1, verbose=False,
                  backend=None):
@@ -1149,14 +1164,17 @@ class ResidualQuantizer:
             raise ValueError(f"ResidualQuantizer: d = {d} and M = {M} must both be at least 1")
         if nbits != 8:
             raise NotImplementedError(f"ResidualQuantizer: nbits = {nbits} (only 8-bit codes, one byte per stage, are implemented)")
-        if max_beam_size != 1:
-            raise NotImplementedError(f"ResidualQuantizer: max_beam_size = {max_beam_size} (only the greedy encoder, a beam "
-                                      "of 1, is implemented)")
+        if not 1 <= max_beam_size <= 32:
+            raise NotImplementedError(f"ResidualQuantizer: max_beam_size = {max_beam_size} (beams of 1 to 32 are "
+                                      "implemented: the exact top-k sweep stops at 32)")
         self.d, self.M, self.nbits, self.max_beam_size = d, M, nbits, max_beam_size
         self.ksub, self.code_size = 256, M
         self.niter, self.seed, self.verbose = int(niter), int(seed), bool(verbose)
         self.max_points_per_centroid = int(max_points_per_centroid)
         self.backend = backend or default_backend()
+        if max_beam_size > 1 and not (hasattr(self.backend, "rq_beam_step") or hasattr(self.backend, "knn")):
+            raise NotImplementedError(f"ResidualQuantizer: max_beam_size = {max_beam_size} needs a backend with "
+                                      "rq_beam_step() or knn()")
         self.centroids_device = None   # [M, ksub, d] device tensor after train() / set_centroids()
         self._centroids_host = None
 
@@ -1189,9 +1207,61 @@ class ResidualQuantizer:
         if not self.is_trained:
             raise RuntimeError(f"ResidualQuantizer.{what}: the quantiser is not trained (call train() or set_centroids())")
 
+    def _beam_step_composed(self, r, b_in, book, b_out):
+        """One beam stage from the backend's knn(): a stable sort on D over the candidates s * k + t, a gather and a
+        subtraction.  Arguments and results as _beam_step."""
+        d = book.shape[1]
+        k = min(b_out, book.shape[0])
+        ids, dis = self.backend.knn(r.reshape(-1, d), book, k)
+        n = ids.shape[0] // b_in
+        ids, dis = ids.view(n, b_in * k), dis.view(n, b_in * k)
+        top, order = torch.sort(dis, dim=1, stable=True)      # equal distances stay in (s, I) order
+        top, order = top[:, :b_out].contiguous(), order[:, :b_out]
+        filled = top < float("inf")
+        parent = torch.where(filled, order // k, torch.zeros_like(order))
+        code = torch.where(filled, ids.gather(1, order), torch.zeros_like(order))
+        rows = torch.arange(n, device=r.device).unsqueeze(1)
+        r_out = r.reshape(n, b_in, d)[rows, parent] - book[code]
+        bad = (~filled).any().reshape(1).to(torch.int32)
+        return r_out.contiguous(), parent.to(torch.int32), code.to(torch.uint8), top, bad
+
+    def _beam_step(self, r, b_in, book, b_out):
+        """One beam stage: r [n, b_in, d] or [n * b_in, d] -> (r_out [n, b_out, d], parent int32, code uint8, dist float32
+        [n, b_out], bad int32 [1]), on the backend's device."""
+        if hasattr(self.backend, "rq_beam_step"):
+            return self.backend.rq_beam_step(r, b_in, book, b_out)
+        return self._beam_step_composed(r, b_in, book, b_out)
+
+    def _encode_by_stages(self, x, cb, want_dist, want_residual, step=None):
+        """The beam encode as one beam stage per codebook (step: _beam_step, or _beam_step_composed) and the walk back
+        from slot 0 through the parents in torch."""
+        step = step or self._beam_step
+        B, ksub = self.max_beam_size, cb.shape[1]
+        r, b = x, 1
+        steps, bad = [], None
+        for m in range(cb.shape[0]):
+            b_out = min(B, b * ksub)
+            r, parent, code, dist, bad_m = step(r, b, cb[m], b_out)
+            steps.append((parent, code, dist))
+            bad = bad_m if bad is None else bad | bad_m
+            b = b_out
+        n = x.shape[0]
+        slot = torch.zeros((n, 1), dtype=torch.int64, device=x.device)
+        codes, dists = [], []
+        for parent, code, dist in reversed(steps):
+            codes.append(code.gather(1, slot))
+            dists.append(dist.gather(1, slot))
+            slot = parent.gather(1, slot).to(torch.int64)
+        return (torch.cat(codes[::-1], 1).contiguous(), torch.cat(dists[::-1], 1).contiguous() if want_dist else None,
+                r[:, 0].contiguous() if want_residual else None, bad)
+
     def _encode(self, x, cb, want_dist, want_residual):
         """-> (codes, dist or None, residual or None, bad int32 [1]) on the backend's device, nothing read back."""
         be = self.backend
+        if self.max_beam_size > 1:
+            if hasattr(be, "rq_beam_encode"):
+                return be.rq_beam_encode(x, cb, self.max_beam_size, want_dist=want_dist, want_residual=want_residual)
+            return self._encode_by_stages(x, cb, want_dist, want_residual)
         if hasattr(be, "rq_encode"):
             return be.rq_encode(x, cb, want_dist=want_dist, want_residual=want_residual)
         r, ids, dis = x, [], []
@@ -1210,14 +1280,18 @@ class ResidualQuantizer:
     def train(self, x) -> None:
         be = self.backend
         r = self._rows(x, "ResidualQuantizer.train")
-        books = []
+        books, b = [], 1
         for m in range(self.M):
             km = Kmeans(self.d, self.ksub, niter=self.niter, verbose=self.verbose, seed=self.seed,
                         max_points_per_centroid=self.max_points_per_centroid, backend=be)
-            km.train(r)
+            km.train(r.reshape(-1, self.d))
             books.append(km.centroids_device)
             if m + 1 < self.M:
-                r = self._encode(r, km.centroids_device.unsqueeze(0), False, True)[2]
+                if self.max_beam_size > 1:
+                    b_out = min(self.max_beam_size, b * self.ksub)
+                    r, b = self._beam_step(r, b, km.centroids_device, b_out)[0], b_out
+                else:
+                    r = self._encode(r, km.centroids_device.unsqueeze(0), False, True)[2]
         self.centroids_device = torch.stack(books, 0).contiguous()
         self._centroids_host = None
 

@@ -20,6 +20,7 @@
  *   faiss.IndexFlatIP(d).search(x, 1), Kmeans(spherical=True) (likewise)   at_assign_ip_f32, at_renorm_rows_f32
  *   faiss.ProductQuantizer(d, M, 8).compute_codes(x) / .decode(codes) (likewise)  at_pq_encode_f32, at_pq_decode_f32
  *   greedy residual quantiser (RVQ, beam 1; the library's own contract)    at_rq_encode_f32, at_rq_decode_f32
+ *   beam-search residual quantiser (beam 1 .. 32; the library's own contract)  at_rq_beam_step_f32, at_rq_beam_encode_f32
  *   torchaudio.transforms.MFCC / ComputeDeltas on log-mel rows (likewise)  at_mfcc_f32, at_deltas_f32,
  *                                                                          at_dct_matrix_host
  *   faiss.Kmeans(d, k, niter).train(x, init_centroids)                     at_rand_perm_mt19937,
@@ -562,7 +563,7 @@ int at_pq_decode_f32(at_ctx* ctx, const uint8_t* codes, int64_t n, int d, int M,
  * and sets *bad.  Then r_{m+1}[i][f] = r_m[i][f] - codebooks[m][codes[i][m]][f], one fp32 subtraction (a flagged row
  * subtracts row 0 like any other; a NaN stays a NaN).  Column M-1 of dist is the squared reconstruction error in the
  * expansion form.  The contract is the library's own, not verified faiss output (faiss's ResidualQuantizer defaults
- * to a beam of 5).
+ * to a beam of 5: at_rq_beam_encode_f32 below).
  *   x: [n][d] fp32; codebooks: [M][ksub][d] fp32; 1 <= ksub <= 256, M >= 1, d >= 1, n >= 0 (n == 0 is a no-op that
  *   touches no pointer); codes: uint8 [n][M]; dist_or_null: float [n][M]; residual_or_null: float [n][d], r_M, must
  *   not overlap x; bad_or_null: DEVICE int32, written by every call with n > 0: 0, then 1 if some row had nothing to
@@ -580,6 +581,43 @@ int at_rq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, int M, int k
  * out are 16-byte aligned, one float per thread otherwise.  No workspace. */
 int at_rq_decode_f32(at_ctx* ctx, const uint8_t* codes, int64_t n, int d, int M, int ksub, const float* codebooks,
                      float* out, void* stream);
+
+/* Residual quantiser, one stage of the beam search.  A row has b_in partial codes (beams), beam s with the residual
+ * r_in[i][s].  (D, I) = at_knn_f32's answer for the n * b_in residuals as ONE [n * b_in][d] call against the codebook
+ * with k = min(b_out, ksub), bit for bit -- so its direct form is chosen by n * b_in < 20.  The candidates of row i are
+ * the (s, t) with I[i * b_in + s][t] >= 0; the new beams are the b_out smallest by (D, s, I), lexicographic and
+ * ascending (equal distances: the lower parent slot, then the lower word; -0 equals +0), slot 0 the best:
+ *   parent[i][s'] = s, code[i][s'] = I, dist[i][s'] = D, r_out[i][s'][f] = r_in[i][s][f] - codebook[I][f], one fp32
+ *   subtraction.
+ * A slot for which no candidate is left (only on rows with NaN, Inf or overflowing distances) follows every filled
+ * slot, takes parent 0, code 0 and distance +inf, subtracts word 0 from parent 0's residual, and sets *bad.
+ *   r_in: [n][b_in][d] fp32; codebook: [ksub][d] fp32; 1 <= ksub <= 256; 1 <= b_in, b_out <= 32, b_out <= b_in * ksub;
+ *   n >= 0 (n == 0 is a no-op that touches no pointer); r_out: [n][b_out][d], must not overlap r_in; parent: int32
+ *   [n][b_out]; code: uint8 [n][b_out]; dist: float [n][b_out]; bad_or_null: DEVICE int32, written by every call with
+ *   n > 0: 0, then 1 if some slot was left unfilled.
+ * One launch behind at_knn_f32's own: nothing is read back.  The select kernel gives a row to a half-wave and moves
+ * 16 bytes per lane where d % 4 == 0 and r_in, r_out and codebook are 16-byte aligned, one float otherwise.  The lists
+ * live in the context: a call on another stream than the context's previous at_rq_beam_* call waits for it. */
+int at_rq_beam_step_f32(at_ctx* ctx, const float* r_in, int64_t n, int b_in, int d, const float* codebook, int ksub,
+                        int b_out, float* r_out, int32_t* parent, uint8_t* code, float* dist, int32_t* bad_or_null,
+                        void* stream);
+
+/* Residual quantiser, beam-search encoder.  B_0 = 1, R_0[i][0] = x[i]; stage m = 0 .. M-1 is at_rq_beam_step_f32 with
+ * b_in = B_m, b_out = B_{m+1} = min(beam, B_m * ksub) and codebooks[m].  codes[i][.] is the path of slot 0 behind the
+ * last stage, dist[i][m] the distance at which that path's stage-m ancestor was chosen (column M-1: the final squared
+ * error in the expansion form), residual[i] = R_M[i][0].  beam = 1 gives at_rq_encode_f32's three outputs bit for bit.
+ * The contract is the library's own (faiss's beam search works from look-up tables of inner products, which changes
+ * the arithmetic; it is not implemented).
+ *   x, codebooks, codes, dist_or_null, residual_or_null, bad_or_null, n, d, M, ksub: as for at_rq_encode_f32;
+ *   1 <= beam <= 32.  *bad is set when any slot of any stage was left unfilled.
+ * Rows are taken in blocks whose workspace (two residual buffers, the lists of one stage, the records of all stages)
+ * stays within 256 MiB; a block of a call with n >= 20 rows never has fewer than 20 (the distance form is the call's).
+ * Per block and stage: at_knn_f32's launches and the select kernel; per block one back-trace kernel.  No host
+ * synchronisation, no device-to-host copy.  A call on another stream than the context's previous at_rq_beam_* call
+ * waits for it. */
+int at_rq_beam_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, int M, int ksub, const float* codebooks,
+                          int beam, uint8_t* codes, float* dist_or_null, float* residual_or_null, int32_t* bad_or_null,
+                          void* stream);
 
 /* ---- MFCC and delta features of log-mel rows (torchaudio.transforms.MFCC, ComputeDeltas; csrc/mfcc.hip) ----------
  * Input: log-mel rows x[g][n], frame-major [n_frames][n_mels] fp32, as at_logmel_f32 / at_logmel_ragged_f32 leave them,
