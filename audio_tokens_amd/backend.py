@@ -53,7 +53,9 @@ class HostHelpers:
         return int(self.lib.at_num_frames(L, hop))
 
     def group_rows_kd(self, rows: np.ndarray, leaf: int = 32) -> np.ndarray:
-        """Spatial grouping of a host table into groups of `leaf` rows (-1 padded permutation)."""
+        """Spatial grouping of a host table into groups of `leaf` rows (-1 padded permutation).  A permutation whatever
+        the table holds (NaN, +-inf, any magnitude); a table scaled by a power of two inside the normal range gets the
+        same cuts."""
         rows = np.ascontiguousarray(rows, dtype=np.float32)
         k, d = rows.shape
         out = np.empty(((k + leaf - 1) // leaf) * leaf, np.int32)
@@ -589,6 +591,11 @@ class HipBackend(HostHelpers):
         return out
 
     def assign(self, x, c, want_dist=True):
+        """Nearest centroid under squared L2 (at_assign_f32): x [n, d], c [k, d] -> (ids [n] int64, dist [n] float32 or
+        None), the oracle's bits; the lowest index on equal distances.  A centroid is a candidate only at a distance
+        below +inf: a row none of whose distances is finite (|x|^2 overflows from finite elements) is (-1, +inf), and a
+        centroid whose own norm overflows is never named.  assign_hinted, assign_pruned, assign_c2f and assign_unguided
+        return the same for any input, whatever they are hinted."""
         x, c = self._f32(x), self._f32(c)
         assert x.dim() == 2 and c.dim() == 2 and x.shape[1] == c.shape[1]
         n, d = x.shape
@@ -821,7 +828,8 @@ class HipBackend(HostHelpers):
         """Same result as assign(), faster when the hints (the previous assignment) are mostly right.
         hint_ids: int64 [n] per row.  order: what centroid_accum(..., want_order=True) returned for
         those ids -- a pair (rows in member-list order, their ids in that order), both uint32 bit
-        patterns in int32 tensors -- or None."""
+        patterns in int32 tensors -- or None.  A hint is only a guess: ids outside [0, k) count as none, and a
+        hinted centroid at distance +inf is not an answer (a row with no finite distance is (-1, +inf))."""
         x, c = self._f32(x), self._f32(c)
         n, d = x.shape
         k = c.shape[0]
@@ -848,7 +856,10 @@ class HipBackend(HostHelpers):
 
     # -- exact pruning for Lloyd iterations ---------------------------------------------------
     def group_min_dist(self, c, cperm) -> torch.Tensor:
-        """cperm: int32 device tensor [ng*32] (-1 padded) -> dmin float32 [k, ng]."""
+        """cperm: int32 device tensor [ng*32] (-1 padded) -> dmin float32 [k, ng]: a lower bound of the distance (not
+        squared) from centroid p to the nearest member of group g; +inf for a group of padding only, 0 wherever no
+        bound can be given (a squared distance that overflows fp32, a table outside the fp16 range under the fp16
+        bound kernels): such a group is always visited."""
         c = self._f32(c)
         k, d = c.shape
         assert cperm.dtype == torch.int32 and cperm.is_contiguous() and cperm.numel() % 32 == 0
@@ -1009,7 +1020,8 @@ class HipBackend(HostHelpers):
         return self.assign_pruned(x, c, self.visit_order(guess, gdis, c.shape[0]), cperm, dmin, want_dist=want_dist)
 
     def assign_pruned(self, x, c, order, cperm, dmin, want_dist=True, mode=0, filter=None, image_current=False):
-        """mode 0: same result as assign(); `order` = visit_order(...) of the guesses.
+        """mode 0: same result as assign() for any input, rows without a finite distance included ((-1, +inf)
+        whatever they guessed); `order` = visit_order(...) of the guesses.
         mode 1: best centroid among the groups named by each 32-row tile (order = visit_order of
         group ids) -- a guess generator.
         filter (default: on unless AT_FILTER=0): fp16-split first stage, same bits out.

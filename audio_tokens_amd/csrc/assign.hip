@@ -8,6 +8,10 @@
 //   xn(i), cn(j) likewise with both operands equal
 //   dis(i,j) = max(0, (xn + cn) - 2*ip)            one rounding for the add, one for the fma
 //   ids[i]   = lowest j with minimal dis, dist[i] = that dis
+//   A centroid is a candidate only with dis < +inf (the strict '<' from +inf): a row none of whose distances is
+//   finite -- |x|^2 overflows from finite elements -- is (-1, +inf) on every route, whatever it was hinted; a
+//   centroid whose |c|^2 is +inf is never named.  The dense epilogue has this from its compare; the hinted and
+//   pruned sweeps, whose exact update breaks ties by index, from no_winner() where they store the answer.
 //
 // Data flow.  The centroid table is re-laid once per call into tiles of 32*NA centroids whose rows
 // are already in LDS order (k split even/odd per 8 features so that one ds_read_b128 feeds four
@@ -70,6 +74,12 @@ __global__ void __launch_bounds__(WG) prep_centroids_kernel(const float* __restr
         out[R * dp + r] = nrm;
     }
 }
+
+// The exact update of the hinted and pruned sweeps accepts a lower index on an EQUAL distance, +inf included, and a
+// running best without a finite distance starts at +inf: a row none of whose distances is finite (|x|^2 overflows)
+// would end with the lowest index its sweep visited.  The contract's strict '<' from +inf never names a centroid at
+// +inf, so such a row is (-1, +inf) -- decided once, where the answer is stored, not in the sweep.
+__device__ __forceinline__ bool no_winner(unsigned fi, float fd) { return fi == 0xffffffffu || !(fd < __builtin_inff()); }
 
 // One arg-min step with the compare mask kept in VCC (three VALU ops, no SGPR pair to carry):
 //   keep = !(dis < bd);  bd = keep ? bd : dis;  br = keep ? br : R
@@ -459,7 +469,7 @@ assign_mfma_hinted_kernel(const float* __restrict__ X, long n, const float* __re
         }
         const long pos = pos0 + 32 * b + j;
         if (h == 0 && pos < n) {
-            ids[rowid[b]] = fi == 0xffffffffu ? -1L : (long)fi;
+            ids[rowid[b]] = no_winner(fi, fd) ? -1L : (long)fi;
             if (dist) dist[rowid[b]] = fd;
         }
     }
@@ -669,7 +679,7 @@ assign_mfma_pruned_kernel(const float* __restrict__ X, long n, const float* __re
         }
         const long pos = pos0 + 32 * b + j;
         if (h == 0 && pos < n) {
-            ids[rowid[b]] = fi == 0xffffffffu ? -1L : (long)fi;
+            ids[rowid[b]] = no_winner(fi, fd) ? -1L : (long)fi;
             if (dist) dist[rowid[b]] = fd;
         }
     }
@@ -832,7 +842,7 @@ assign_mfma_pruned_reg_kernel(const float* __restrict__ X, long n, const float* 
         }
         const long pos = pos0 + 32 * b + j;
         if (h == 0 && pos < n) {
-            ids[rowid[b]] = fi == 0xffffffffu ? -1L : (long)fi;
+            ids[rowid[b]] = no_winner(fi, fd) ? -1L : (long)fi;
             if (dist) dist[rowid[b]] = fd;
         }
     }

@@ -275,6 +275,10 @@ struct at_diag_counters {
 extern at_diag_counters g_at_diag;          // host.cpp (one per process; the counts are diagnostics, not state)
 extern int g_at_strict_errors;              // host.cpp: switch strict_errors (AT_STRICT_ERRORS), process-wide
 
+// host.cpp: tests for NaN / inf that a -ffast-math translation unit (host_group.cpp) can rely on
+bool at_is_finite_f32(float v);
+void at_zero_nonfinite_f32(float* v, size_t n);
+
 hipError_t at_hip_tolerated(hipError_t e, const char* file, int line);
 // returns hipSuccess, or -- strict mode -- the pending error
 hipError_t at_stale_check(const char* file, int line);

@@ -201,9 +201,9 @@ assign_f16filter_kernel(const float* __restrict__ X, long n, const unsigned char
             if (h == 0 && pos0 + 32 * b + j < n) fp.bd_out[pos] = bd;
             const float delta = (2.0f * D + 8.0f) * 5.9604645e-8f * (xn + cnmax) * 1.01f;
             // rows without a guess need every group; positions past n need none
-            mtau[b] = pos0 + 32 * b + j >= n ? -1.0f
-                                             : (has ? 2.0f * sqrtf(dh + delta) * (1.0f + 4.0f * 5.9604645e-8f) + 1e-30f
-                                                    : __builtin_inff());
+            float t2r = has ? 2.0f * sqrtf(dh + delta) * (1.0f + 4.0f * 5.9604645e-8f) + 1e-30f : __builtin_inff();
+            if (!(t2r == t2r)) t2r = __builtin_inff();  // NaN would read as "past n" below: look everywhere
+            mtau[b] = pos0 + 32 * b + j >= n ? -1.0f : t2r;
         }
 #pragma unroll
         for (int s = 0; s < NS; s++) {
@@ -880,8 +880,9 @@ __device__ __forceinline__ void exact_rows_body(unsigned vblock, unsigned vgrid,
             const float d1 = __builtin_fmaxf(__builtin_fmaf(-2.0f, ip1, xn + cn1), 0.0f);
             const float d2 = __builtin_fmaxf(__builtin_fmaf(-2.0f, ip2, xn + cn2), 0.0f);
             const bool take2 = d2 < d1 || (d2 == d1 && (long)second < p);   // lowest index on a tie
-            ids[row] = take2 ? (long)second : p;
-            if (dist) dist[row] = take2 ? d2 : d1;
+            const float dw = take2 ? d2 : d1;
+            ids[row] = dw < __builtin_inff() ? (take2 ? (long)second : p) : -1L;   // (+inf never wins: assign.hip, no_winner)
+            if (dist) dist[row] = dw;
         }
     }
     for (unsigned entry_e = vblock; entry_e < count; entry_e += vgrid) {
@@ -963,7 +964,8 @@ __device__ __forceinline__ void exact_rows_body(unsigned vblock, unsigned vgrid,
                 bd = red_d[w];
                 bi = red_i[w];
             }
-        ids[row] = bi == NONE ? -1L : (long)bi;
+        // (the lexicographic reduction above lets equal distances tie at +inf too; the contract does not: no_winner)
+        ids[row] = (bi == NONE || !(bd < __builtin_inff())) ? -1L : (long)bi;
         if (dist) dist[row] = bd;
     }
     __syncthreads();  // the shared scratch is reused by the next entry

@@ -213,6 +213,19 @@ int64_t at_workspace_bytes(const at_ctx* ctx) {
 
 }  // extern "C"
 
+// For host_group.cpp, which is compiled with -ffast-math: there a test for NaN or inf -- even one written on the
+// bits -- may be assumed false and removed, so the tests live in this translation unit.
+bool at_is_finite_f32(float v) {
+    uint32_t b;
+    std::memcpy(&b, &v, sizeof b);
+    return (b & 0x7f800000u) != 0x7f800000u;
+}
+
+void at_zero_nonfinite_f32(float* v, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!at_is_finite_f32(v[i])) v[i] = 0.0f;
+}
+
 int at_guard_enter(at_ws_guard* g, hipStream_t stream) {
     if (!g->ev) AT_HIP(hipEventCreateWithFlags(&g->ev, hipEventDisableTiming));
     if (g->used && g->stream != stream) AT_HIP(hipStreamWaitEvent(stream, g->ev, 0));

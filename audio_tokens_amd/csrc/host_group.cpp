@@ -24,7 +24,7 @@ int at_group_rows_kd_host(const float* rows, int k, int d, int leaf, int32_t* pe
     std::vector<Part> stack{{0, k, 0, ngroups}};
     std::vector<int> bounds((size_t)ngroups + 1, 0);
     bounds[ngroups] = k;
-    std::vector<float> meanf((size_t)d), axisf((size_t)d), nextf((size_t)d), proj((size_t)k), cen;
+    std::vector<float> meanf((size_t)d), axisf((size_t)d), nextf((size_t)d), proj((size_t)k), part_proj((size_t)k), cen;
     while (!stack.empty()) {
         const Part p = stack.back();
         stack.pop_back();
@@ -46,6 +46,20 @@ int at_group_rows_kd_host(const float* rows, int k, int d, int leaf, int32_t* pe
             float* c = cen.data() + (size_t)i * d;
             for (int f = 0; f < d; f++) c[f] = r[f] - meanf[f];
         }
+        // bring the part to about magnitude 1 by a power of two: the sums below hold products of three and four
+        // coordinates, which leave the fp32 range from about 2^32 per coordinate, and a NaN projection would leave
+        // the comparator of nth_element without an order.  The factor is a normal number (exponent within +-126: a
+        // part whose largest coordinate is at 2^127 ends in [1, 4), a subnormal one below 1), so the product is exact
+        // for every coordinate that stays normal, and a table scaled by a power of two gets the same cuts as long as
+        // its sums and its smaller coordinates stay inside the normal range.
+        float mx = 0.0f;
+        for (size_t e = 0; e < (size_t)m * d; e++) mx = std::max(mx, std::fabs(cen[e]));
+        if (at_is_finite_f32(mx) && mx > 0.0f) {
+            int ex = 0;
+            std::frexp(mx, &ex);
+            const float s = std::ldexp(1.0f, -std::min(std::max(ex, -126), 126));
+            for (size_t e = 0; e < (size_t)m * d; e++) cen[e] *= s;
+        }
         // principal axis by power iteration (deterministic start)
         for (int f = 0; f < d; f++) axisf[f] = 1.0f + 0.01f * (float)f;
         for (int it = 0; it < 4; it++) {
@@ -66,8 +80,10 @@ int at_group_rows_kd_host(const float* rows, int k, int d, int leaf, int32_t* pe
             const float* c = cen.data() + (size_t)i * d;
             float t = 0.0f;
             for (int f = 0; f < d; f++) t += c[f] * axisf[f];
-            proj[idx[p.lo + i]] = t;
+            part_proj[i] = t;
         }
+        at_zero_nonfinite_f32(part_proj.data(), (size_t)m);   // (rows with non-finite values: anywhere, but ordered)
+        for (int i = 0; i < m; i++) proj[idx[p.lo + i]] = part_proj[i];
         const int gmid = p.g0 + (p.g1 - p.g0) / 2;
         int cut = p.lo + (gmid - p.g0) * leaf;  // left side = whole groups
         if (cut > p.hi) cut = p.hi;

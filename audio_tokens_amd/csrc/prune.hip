@@ -14,6 +14,14 @@
 // (a lower bound of) |c - c_p| > 2 R.  Centroids are handled in groups of 32 (one MFMA
 // accumulator) laid out by a kd-style spatial grouping, rows in tiles of 32 visited in
 // (previous centroid, distance) order so that the outliers of a cluster sit together.
+// At the ends of the fp32 range the real-number argument needs two guards (tests/test_gpu_magnitude.py):
+// the direct sum |c - c_p|^2 overflows from |c - c_p| ~ 1.84e19 although the sweep's (xn + cn) - 2 ip
+// is finite for rows between the two, so a sum that is not finite bounds nothing (dmin = 0); and a radius
+// that comes out NaN (a non-finite row, a NaN centroid norm) compares false with every dmin, so it is read
+// as +inf.  A row with |x|^2 = +inf has delta = +inf and visits every group; it ends as (-1, +inf)
+// (assign.hip, no_winner).  Subnormal sums need nothing: delta's relative model is a handful of
+// subnormal ulps there, but the bound kernel's 2e-5 and the sqrt absorb the absolute half-ulp per step
+// (measured: the 2^-64 rung prunes like the unit one and keeps every bit).
 //   group_min_dist_kernel : dmin[p][g] = lower bound of min_{c in group g} |c - c_p|
 //   visit order           : stable radix sort of (p << 8 | quantised distance, row)
 //   prune_mask_kernel     : per row bd; per 32-row tile one bit per group ("some row needs it")
@@ -69,7 +77,10 @@ __global__ void __launch_bounds__(WG) group_min_dist_kernel(const float* __restr
             s0 = __builtin_fmaf(d2, d2, s0);
             s1 = __builtin_fmaf(d3, d3, s1);
         }
-        best = fminf(best, s0 + s1);
+        // |c_p - c_m|^2 overflows from |c_p - c_m| ~ 1.84e19 while the sweep's (xn + cn) - 2 ip is still finite for rows
+        // between the two: a sum that is not finite bounds nothing (0: the group is always visited)
+        const float s = s0 + s1;
+        best = fminf(best, s < __builtin_inff() ? s : 0.0f);
     }
     // the fp32 sum of squared fp32 differences is within (d+3)u of the true value: shave 2e-5
     if (livep) dmin[(size_t)p * ng + g] = best == __builtin_inff() ? best : sqrtf(best) * (1.0f - 2e-5f);
@@ -161,8 +172,9 @@ __global__ void __launch_bounds__(WG) prune_mask_kernel(const float* __restrict_
     const float cnmax = __uint_as_float(*cnmax_bits);
     const float delta = (2.0f * D + 8.0f) * U32 * (xn + cnmax) * 1.01f;
     // rows without a guess need every group; positions past n need none
-    const float tau = !live ? -1.0f
-                            : (has ? 2.0f * sqrtf(dh + delta) * (1.0f + 4.0f * U32) + 1e-30f : __builtin_inff());
+    float tau = has ? 2.0f * sqrtf(dh + delta) * (1.0f + 4.0f * U32) + 1e-30f : __builtin_inff();
+    if (!(tau == tau)) tau = __builtin_inff();  // NaN (a non-finite row or centroid norm) compares false: look everywhere
+    if (!live) tau = -1.0f;
 
     // Rows arrive sorted by guess, so a 32-row tile holds a few runs of equal p: a group is needed by
     // the tile iff dmin[p][g] <= the largest tau of some run.  Lanes stand for groups here (64 per
