@@ -92,6 +92,10 @@ SIGNATURES = {
     "at_filter_probe_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                    _c.POINTER(_i64), _vp]),
     "at_prune_peek": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    "at_block_sched_install": (_i32, [_vp, _vp, _i64]),
+    "at_block_sched_peek": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _c.POINTER(_i32), _vp]),
+    "at_block_sched_last": (_i32, [_vp, _c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64)]),
+    "at_block_sched_limits": (_i32, [_c.POINTER(_i64), _c.POINTER(_i64)]),
     "at_group_means_f32": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "at_group_neighbours_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "at_assign_pruned_f32": (_i32, [_vp, _vp, _vp]),   # (ctx, const at_pruned_args*, stream)

@@ -1096,6 +1096,38 @@ class HipBackend(HostHelpers):
             _lib.check(self.lib.at_prune_peek(self.ctx.handle, n, ng, _ptr(bd), _ptr(mask), self._stream()))
         return bd, mask
 
+    def block_sched_install(self, sched) -> None:
+        """Test hook: the exact filter sweeps of exactly len(sched) row blocks start their blocks in this order (a
+        permutation of range(len(sched)), else refused); None removes it."""
+        a = np.ascontiguousarray(sched, dtype=np.uint32) if sched is not None else np.zeros(0, np.uint32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_block_sched_install(self.ctx.handle, a.ctypes.data if a.size else None, a.size))
+
+    def block_sched_peek(self, order, tiles):
+        """Test hook: (table int32 [blocks], weights uint8 [ceil(n / 32)]) that visit_order made beside `order` (its
+        first output) for row blocks of `tiles` tiles, or None when the context holds no table with that tag."""
+        n = order.numel()
+        nt = (n + 31) // 32
+        table, weight = self.empty(((nt + tiles - 1) // tiles,), torch.int32), self.empty((nt,), torch.uint8)
+        found = ctypes.c_int(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_block_sched_peek(self.ctx.handle, _ptr(order), n, tiles, _ptr(table), _ptr(weight),
+                                                    ctypes.byref(found), self._stream()))
+        return (table, weight) if found.value else None
+
+    def block_sched_last(self):
+        """Test hook: (path, tiles per block, blocks) of the last filter sweep; path 0 = visiting order, 1 = a table made
+        beside its order, 2 = the installed schedule."""
+        p, t, b = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+        _lib.check(self.lib.at_block_sched_last(self.ctx.handle, ctypes.byref(p), ctypes.byref(t), ctypes.byref(b)))
+        return int(p.value), int(t.value), int(b.value)
+
+    def block_sched_limits(self):
+        """(rows up to which an exact d = 64 sweep runs one tile per wave, ... two tiles per wave)."""
+        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(self.lib.at_block_sched_limits(ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
     def rand_perm_prefix_device(self, n: int, seed: int, m: int) -> torch.Tensor:
         """First m entries of faiss' rand_perm(n, seed) as a device int32 tensor, computed on the device
         (no host work, no upload); same bits as HostHelpers.rand_perm_prefix."""

@@ -102,6 +102,8 @@ enum at_ws_slot {
     WS_RQ_BEAM_RES,    // at_rq_beam_encode_f32: the two residual buffers [rows][B][d] of a block of rows
     WS_RQ_BEAM_LISTS,  // at_rq_beam_step_f32 / _encode_f32: the at_knn_f32 lists of one stage (ids, then distances)
     WS_RQ_BEAM_PATH,   // at_rq_beam_encode_f32: (parent, distance, word) of every slot of every stage of a block of rows
+    WS_BLOCK_SCHED,    // at_visit_order_f32: the two halves of the block schedules (exact_plan.h SchedLayout), by call parity
+    WS_BLOCK_SCHED_HOOK,   // at_block_sched_install: the caller's schedule
     WS_NSLOTS
 };
 
@@ -153,6 +155,7 @@ struct at_debug {
     int logmel_fallback;  // AT_LOGMEL_FALLBACK  1 = Bluestein form of the log-mel transform for every n_fft that is not a power of two
     int ap_ws_mb;         // AT_AP_WS_MB         MiB the two key buffers of a class chunk of at_average_precision_f32 may take (default 1024; -m = chunks of m classes)
     int filter_timing;    // AT_FILTER_TIMING    1 = exact calls bracket their stage-1 kernel with two timing events (bench.py; off in the product)
+    int block_sched;      // AT_BLOCK_SCHED      0 = the exact filter sweeps start their row blocks in visiting order
 };
 
 // What a log-mel table slot holds (WS_LOGMEL_FB: the tuned 512-point kernel's tables; WS_LOGMEL_ANY: every other
@@ -189,6 +192,25 @@ enum at_guard_id {
     AT_GUARD_RQ_BEAM,   // at_rq_beam_step_f32 / at_rq_beam_encode_f32: WS_RQ_BEAM_* (they call at_knn_f32, which takes
                         // AT_GUARD_KNN on the same stream inside: guards do not nest on one another's slots)
     AT_NGUARDS
+};
+
+// The block schedules of the exact filter sweeps (exact_plan.h: SchedLayout, sched_path).  at_visit_order_f32 call
+// number j writes half j & 1 of WS_BLOCK_SCHED, so the table a running sweep reads -- that of the order before -- is not
+// rewritten by a visit order that runs beside it on another stream.  Every user of a half, reader or writer, also goes
+// through the half's guard (at_ws_guard: one event, one stream): it enters before it touches the half -- on another
+// stream than the user before it, that is a wait for that user's leave event -- and leaves behind its last launch.  So
+// the users of a half run one after the other in the order of their calls (contexts are used from one host thread), two
+// sweeps over one order on two streams included: the second waits for the first, the next writer for the second.  A
+// caller who strays from the Lloyd pattern waits, and never reads a torn table.  Both halves are laid out for one row
+// count; a call with another n lays the slot out anew and drops what either half held.
+struct at_block_sched_state {
+    exact_plan::SchedTag tag[2];
+    at_ws_guard guard[2];
+    int64_t layout_n;          // the row count WS_BLOCK_SCHED is laid out for (0 = nothing)
+    unsigned calls;            // at_visit_order_f32 calls that made tables
+    int64_t installed_blocks;  // at_block_sched_install: blocks of the schedule in WS_BLOCK_SCHED_HOOK (0 = none)
+    int last_path, last_tiles; // what the last filter sweep took (at_block_sched_last)
+    int64_t last_blocks;
 };
 
 struct at_ctx {
@@ -228,6 +250,7 @@ struct at_ctx {
     int mfcc_dct_nmfcc, mfcc_dct_nmels;   // what WS_MFCC_DCT holds (0 = nothing)
     int64_t prepass_n;                    // rows and groups of the last at_prune_prepass (what WS_PRUNE_BD / WS_PRUNE_MASK
     int prepass_ng;                       // hold; 0 = nothing): at_prune_peek refuses any other size
+    at_block_sched_state sched;
 };
 
 // host.cpp.  enter: before the call touches the guarded slots (the event is created on first use, timing disabled; the
@@ -382,6 +405,12 @@ int at_pruned_sweep_f32(at_ctx* ctx, const at_exact_call& call, int64_t n, const
 // dist_out: guess distances / a guess generator's approximate ones; approx_out: at_filter_probe_f32)
 int at_filter_sweep(at_ctx* ctx, const at_exact_call& call, int collect, bool fused_prepass, float* dist_out,
                     float* approx_out);
+// exact_search.cpp: the block order of a filter sweep of `blocks` row blocks of `tiles` tiles (exact_plan::sched_path):
+// *sched = the table to start the blocks by, null = in visiting order; *half = the half of WS_BLOCK_SCHED it sits in
+// (the stream has entered its guard: at_block_sched_release behind the launch), or -1
+int at_block_sched_pick(at_ctx* ctx, const at_exact_call& call, bool exact_sweep, int tiles, int64_t blocks,
+                        const uint32_t** sched, int* half);
+int at_block_sched_release(at_ctx* ctx, int half, hipStream_t stream);
 // ... the distance passes and the redo of the listed rows (m: list length, or the number of workgroups to launch)
 int at_exact_dist_todo(at_ctx* ctx, const at_exact_call& call);
 int at_exact_dist_rows(at_ctx* ctx, const at_exact_call& call);

@@ -164,6 +164,111 @@ int exact_search(at_ctx* ctx, at_exact_call& call, int mode, bool prepass_done, 
 
 }  // namespace
 
+// ---- block schedules (exact_plan.h: sched_path; made in prune.hip beside the visiting order) -------------------------
+// Why a sweep may start its blocks by a table: any permutation of the blocks of a launch gives the same output (each
+// block records its rows by position), so a table that is stale -- made for an order that has
+// since been overwritten in place, or whose buffer now holds another order of the same n -- costs speed at most.  A
+// table of another row count, or one read while it is rewritten, could name a block twice and another never: hence
+// the tag (order buffer, n), the two halves by call parity, their guards, and the visiting order as the fall-back.
+int at_block_sched_pick(at_ctx* ctx, const at_exact_call& call, bool exact_sweep, int tiles, int64_t blocks,
+                        const uint32_t** sched, int* half) {
+    at_block_sched_state& s = ctx->sched;
+    *sched = nullptr;
+    *half = -1;
+    const exact_plan::SchedPath path = exact_plan::sched_path(ctx->dbg.block_sched, exact_sweep, call.order, call.n, tiles, blocks,
+                                                              s.tag[0], s.tag[1], s.installed_blocks);
+    s.last_path = (int)path;
+    s.last_tiles = tiles;
+    s.last_blocks = blocks;
+    if (path == exact_plan::SCHED_INSTALLED) {
+        *sched = static_cast<const uint32_t*>(ctx->ws[WS_BLOCK_SCHED_HOOK]);
+    } else if (path == exact_plan::SCHED_TABLE0 || path == exact_plan::SCHED_TABLE1) {
+        const int h = path == exact_plan::SCHED_TABLE1;
+        const exact_plan::SchedLayout l = exact_plan::sched_layout(call.n);
+        AT_REQUIRE(s.layout_n == call.n && ctx->ws[WS_BLOCK_SCHED] && ctx->ws_bytes[WS_BLOCK_SCHED] >= 2 * l.bytes &&
+                       l.blocks[exact_plan::sched_table_index(tiles)] == blocks,
+                   "at_block_sched_pick: the tables are not those of n=%lld", (long long)call.n);
+        const int rc = at_guard_enter(&s.guard[h], call.stream);   // (made on another stream: wait for it)
+        if (rc) return rc;
+        *sched = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(ctx->ws[WS_BLOCK_SCHED]) + (size_t)h * l.bytes +
+                                                   l.table_off[exact_plan::sched_table_index(tiles)]);
+        *half = h;
+    }
+    return AT_OK;
+}
+
+int at_block_sched_release(at_ctx* ctx, int half, hipStream_t stream) { return at_guard_leave(&ctx->sched.guard[half], stream); }
+
+// Test hook: a caller-made schedule for the filter sweeps of exactly `blocks` row blocks (host array; it must be a
+// permutation of [0, blocks): anything else would leave rows unanswered).  blocks = 0 removes it.  Waits for the device.
+extern "C" int at_block_sched_install(at_ctx* ctx, const uint32_t* sched_host, int64_t blocks) {
+    AT_REQUIRE(ctx && blocks >= 0 && blocks < (int64_t)UINT32_MAX && (sched_host || blocks == 0), "at_block_sched_install: bad arguments");
+    AT_HIP(hipSetDevice(ctx->device));
+    AT_HIP(hipDeviceSynchronize());   // no sweep is reading the schedule it replaces
+    ctx->sched.installed_blocks = 0;
+    if (blocks == 0) return AT_OK;
+    std::vector<bool> seen((size_t)blocks, false);
+    for (int64_t i = 0; i < blocks; i++) {
+        const uint32_t b = sched_host[i];
+        AT_REQUIRE((int64_t)b < blocks && !seen[b], "at_block_sched_install: not a permutation of [0, %lld) (entry %lld = %u)",
+                   (long long)blocks, (long long)i, b);
+        seen[b] = true;
+    }
+    void* dev = at_ws(ctx, WS_BLOCK_SCHED_HOOK, sizeof(uint32_t) * (size_t)blocks, nullptr);
+    if (!dev) return AT_E_NOMEM;
+    AT_HIP(hipMemcpy(dev, sched_host, sizeof(uint32_t) * (size_t)blocks, hipMemcpyHostToDevice));
+    ctx->sched.installed_blocks = blocks;
+    return AT_OK;
+}
+
+// Test hook: the table of blocks of `tiles` tiles (1, 2, 4) made beside `order` (the order_out of an at_visit_order_f32
+// of n rows), copied to the caller's DEVICE buffer [ceil(ceil(n / 32) / tiles)] in stream order, with the tile weights
+// (DEVICE bytes [ceil(n / 32)], may be null); *found = 0 and nothing copied when no table carries that tag.
+extern "C" int at_block_sched_peek(at_ctx* ctx, const uint32_t* order, int64_t n, int tiles, uint32_t* table_out,
+                                   unsigned char* weight_out, int* found, void* stream_) {
+    AT_REQUIRE(ctx && order && n > 0 && table_out && found && exact_plan::sched_table_index(tiles) >= 0,
+               "at_block_sched_peek: bad arguments");
+    at_block_sched_state& s = ctx->sched;
+    *found = 0;
+    int h = -1;
+    for (int i = 0; i < 2; i++)
+        if (h < 0 && s.tag[i].valid && s.tag[i].order == order && s.tag[i].n == n) h = i;
+    if (h < 0) return AT_OK;
+    const exact_plan::SchedLayout l = exact_plan::sched_layout(n);
+    AT_REQUIRE(s.layout_n == n && ctx->ws[WS_BLOCK_SCHED] && ctx->ws_bytes[WS_BLOCK_SCHED] >= 2 * l.bytes,
+               "at_block_sched_peek: the tables are not those of n=%lld", (long long)n);
+    AT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = at_guard_enter(&s.guard[h], stream);
+    if (rc) return rc;
+    const unsigned char* base = static_cast<const unsigned char*>(ctx->ws[WS_BLOCK_SCHED]) + (size_t)h * l.bytes;
+    const int t = exact_plan::sched_table_index(tiles);
+    AT_HIP(hipMemcpyAsync(table_out, base + l.table_off[t], sizeof(uint32_t) * (size_t)l.blocks[t], hipMemcpyDeviceToDevice, stream));
+    if (weight_out) AT_HIP(hipMemcpyAsync(weight_out, base + l.weight_off, (size_t)l.tiles, hipMemcpyDeviceToDevice, stream));
+    rc = at_guard_leave(&s.guard[h], stream);
+    if (rc) return rc;
+    *found = 1;
+    return AT_OK;
+}
+
+// Test hook: what the last filter sweep of the context started its blocks by (0 = visiting order, 1 = a table made
+// beside its order, 2 = the installed schedule), its tiles per block and its number of blocks.  No device work.
+extern "C" int at_block_sched_last(at_ctx* ctx, int* path, int* tiles, int64_t* blocks) {
+    AT_REQUIRE(ctx && path, "at_block_sched_last: bad arguments");
+    const int p = ctx->sched.last_path;
+    *path = p == exact_plan::SCHED_IDENTITY ? 0 : p == exact_plan::SCHED_INSTALLED ? 2 : 1;
+    if (tiles) *tiles = ctx->sched.last_tiles;
+    if (blocks) *blocks = ctx->sched.last_blocks;
+    return AT_OK;
+}
+
+// The row counts up to which an exact d = 64 sweep with the fused pre-pass runs one / two tiles per wave.  No device work.
+extern "C" int at_block_sched_limits(int64_t* one_tile_max_rows, int64_t* two_tile_max_rows) {
+    if (one_tile_max_rows) *one_tile_max_rows = exact_plan::ONE_TILE_MAX_ROWS;
+    if (two_tile_max_rows) *two_tile_max_rows = exact_plan::TWO_TILE_MAX_ROWS;
+    return AT_OK;
+}
+
 int at_filter_use_slot(at_ctx* ctx, int slot) {
     AT_REQUIRE(slot >= 0 && slot <= AT_FILTER_RING, "at_filter_use_slot: slot %d out of range", slot);
     at_filter_state& f = ctx->filter;

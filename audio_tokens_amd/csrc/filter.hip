@@ -101,7 +101,8 @@ assign_f16filter_kernel(const float* __restrict__ X, long n, const unsigned char
                         const uint32_t* __restrict__ mask, int ngw, unsigned* __restrict__ misc, float tau_a,
                         float tau_b, float rho_a, float rho_b, int screen, int collect, long* __restrict__ ids,
                         uint32_t* __restrict__ amb_list, uint32_t* __restrict__ amb_aux,
-                        float* __restrict__ approx_out, FusedPrepass fp, uint4* __restrict__ blk_stats, unsigned amb_cap) {
+                        float* __restrict__ approx_out, FusedPrepass fp, uint4* __restrict__ blk_stats, unsigned amb_cap,
+                        const uint32_t* __restrict__ sched) {
     static_assert(NB == 1 || NB == 2 || NB == 4, "tiles are processed in pairs (NB = 1: a pair whose second tile does not exist)");
     // blk_stats (may be null = statistics off): one record per workgroup {groups needed, groups of the dense sweep,
     // tiles multiplied hi*hi, tiles refined}, summed by filter_stats_reduce_kernel.  Round 1 added these with
@@ -122,7 +123,10 @@ assign_f16filter_kernel(const float* __restrict__ X, long n, const unsigned char
     const int lane = threadIdx.x;
     const int j = lane & 31;
     const int h = lane >> 5;
-    const long pos0 = (long)blockIdx.x * (32 * NB);
+    // The row block of this workgroup: by the schedule of the launch (exact_plan.h: widest need sets first), else in
+    // visiting order.  Any permutation of the blocks gives the same output: every block records its rows by position.
+    // (blockIdx.x itself stays the index of the statistics record and of the redo sub-list, which may be any.)
+    const long pos0 = (long)(sched ? sched[blockIdx.x] : blockIdx.x) * (32 * NB);
     const long ntile32 = (n + 31) / 32;
     const float cnmax = __uint_as_float(misc[0]);
     const bool c_bad = !(cnmax < RANGE_SQ);
@@ -1186,12 +1190,11 @@ int at_filter_sweep(at_ctx* ctx, const at_exact_call& call, int collect, bool fu
     // tiles per wave at three waves per SIMD (168 registers, no second fragment set: occupancy hides the
     // loads; 3 % faster than four tiles at two waves); the long tokenise sweeps and the guess generators
     // keep four tiles per wave.  AT_FILTER_NB=1|2|4 forces the choice (A/B aid).
-    const int nbv = ctx->dbg.filter_nb;
     // Short sweeps (a shard of an N-GPU run: 262 144 rows are 4096 two-tile waves for 3072 slots, i.e. two rounds where
     // 1.33 would do) run ONE tile per wave at four waves per SIMD: 8192 half-size waves on 4096 slots.
-    const bool one_tile = fused && d == 64 && !ctx->dbg.filter_wps2 && (nbv ? nbv == 1 : n <= (int64_t)1 << 19);
-    const bool wps3 = !one_tile && fused && d == 64 && (nbv ? nbv == 2 : n <= (int64_t)8 << 20) && !ctx->dbg.filter_wps2;
-    const int NB = one_tile ? 1 : (wps3 || nbv == 2) ? 2 : 4;
+    const exact_plan::SweepShape shape = exact_plan::sweep_shape(fused, d, n, ctx->dbg.filter_nb, ctx->dbg.filter_wps2);
+    const int NB = shape.tiles;
+    const bool one_tile = shape.tiles == 1, wps3 = shape.wps == 3;
     const dim3 grid((unsigned)((n + 32 * NB - 1) / (32 * NB)));
     AT_REQUIRE(d == 64 || d == 128, "at_filter_sweep: d must be 64 or 128");
     // statistics (switch filter_stats; off by default): one record per workgroup, summed behind the sweep
@@ -1204,6 +1207,14 @@ int at_filter_sweep(at_ctx* ctx, const at_exact_call& call, int collect, bool fu
     // exact calls under the switch filter_timing (bench.py): two timing events around the kernel, read by
     // at_filter_resolve_pending / the synchronous form once the call's statistics have arrived.  The product leaves
     // the switch off: no event is recorded and none is read.
+    // the order the row blocks start in: a table made beside this very order (widest need sets first), a schedule
+    // installed through the debug hook, or -- guess generators, orders made elsewhere -- the visiting order
+    const uint32_t* sched = nullptr;
+    int sched_half = -1;
+    {
+        const int rc = at_block_sched_pick(ctx, call, collect != 0, NB, (int64_t)grid.x, &sched, &sched_half);
+        if (rc) return rc;
+    }
     at_filter_slot& tslot = ctx->filter.ring[(ctx->filter.slot >= 0 && ctx->filter.slot <= AT_FILTER_RING) ? ctx->filter.slot : AT_FILTER_RING];
     const bool timed = collect && ctx->dbg.filter_timing != 0;
     tslot.timed = 0;
@@ -1216,7 +1227,7 @@ int at_filter_sweep(at_ctx* ctx, const at_exact_call& call, int collect, bool fu
 #define AT_FILTER_LAUNCH(DD, NBB, GG, FF, WW, GRID)                                                                   \
     AT_LAUNCH((assign_f16filter_kernel<DD, NBB, GG, FF, WW>), GRID, dim3(64), 0, stream, x, (long)n, img, ng, order, \
                        bd, mask, ngw, misc, ta, tb, ra, rb, screen, collect, reinterpret_cast<long*>(ids), amb_list,      \
-                       amb_aux, approx_out, fp, blk_stats, amb_cap)
+                       amb_aux, approx_out, fp, blk_stats, amb_cap, sched)
     // exact calls (collect) and guess generators are separate instantiations: the guess path's code
     // would otherwise cost the exact sweep registers it does not have
     const dim3 grid64((unsigned)((n + 63) / 64));
@@ -1237,6 +1248,10 @@ int at_filter_sweep(at_ctx* ctx, const at_exact_call& call, int collect, bool fu
     if (timed) {
         AT_HIP(hipEventRecord(tslot.ev[1], stream));
         tslot.timed = 1;
+    }
+    if (sched_half >= 0) {   // (behind the timing event: the guard's event is no part of the kernel's time)
+        const int rc = at_block_sched_release(ctx, sched_half, stream);
+        if (rc) return rc;
     }
     if (blk_stats) {
         AT_LAUNCH(filter_stats_reduce_kernel, dim3(1), dim3(1024), 0, stream, blk_stats, n_wg, fused ? fp.stats : nullptr, misc);
@@ -1401,10 +1416,10 @@ int at_filter_coarse(at_ctx* ctx, const float* x, int64_t n, int d, const float*
     if (d == 128)
         AT_LAUNCH((assign_f16filter_kernel<128, 2, true, false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, x,
                            (long)n, img, ng, no_order, no_bd, no_mask, ngw, misc, ta, tb, ra, rb, 1, 0,
-                           reinterpret_cast<long*>(ids), no_list, no_list, no_approx, fp, static_cast<uint4*>(nullptr), 0u);
+                           reinterpret_cast<long*>(ids), no_list, no_list, no_approx, fp, static_cast<uint4*>(nullptr), 0u, no_order);
     else
         AT_LAUNCH((assign_f16filter_kernel<64, 4, true, false>), dim3((unsigned)((n + 127) / 128)), dim3(64), 0, stream, x,
                            (long)n, img, ng, no_order, no_bd, no_mask, ngw, misc, ta, tb, ra, rb, 1, 0,
-                           reinterpret_cast<long*>(ids), no_list, no_list, no_approx, fp, static_cast<uint4*>(nullptr), 0u);
+                           reinterpret_cast<long*>(ids), no_list, no_list, no_approx, fp, static_cast<uint4*>(nullptr), 0u, no_order);
     return AT_OK;
 }

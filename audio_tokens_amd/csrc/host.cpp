@@ -72,6 +72,7 @@ const DebugField kDebugFields[] = {
     {"filter_timing", "AT_FILTER_TIMING", &at_debug::filter_timing, 0},
     {"logmel_fallback", "AT_LOGMEL_FALLBACK", &at_debug::logmel_fallback, 0},
     {"ap_ws_mb", "AT_AP_WS_MB", &at_debug::ap_ws_mb, 1024},
+    {"block_sched", "AT_BLOCK_SCHED", &at_debug::block_sched, 1},
 };
 }  // namespace
 
@@ -184,6 +185,8 @@ void at_destroy(at_ctx* ctx) {
     if (ctx->background_stream) (void)AT_HIP_TOLERATE(hipStreamDestroy(ctx->background_stream));
     if (ctx->mt_ready) (void)AT_HIP_TOLERATE(hipEventDestroy(ctx->mt_ready));
     for (at_ws_guard& g : ctx->guard)
+        if (g.ev) (void)AT_HIP_TOLERATE(hipEventDestroy(g.ev));
+    for (at_ws_guard& g : ctx->sched.guard)
         if (g.ev) (void)AT_HIP_TOLERATE(hipEventDestroy(g.ev));
     if (ctx->filter.host_misc) (void)AT_HIP_TOLERATE(hipHostFree(ctx->filter.host_misc));
     at_logmel_tables_clear(&ctx->lm_fb);

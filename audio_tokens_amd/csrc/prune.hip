@@ -102,15 +102,149 @@ __global__ void __launch_bounds__(WG) visit_keys_kernel(const long* __restrict__
     vals[i] = (uint32_t)i;
 }
 
-// the sorted keys give the guesses in visiting order; the sorted values (row indices) leave the sort's buffer in the same pass
+// the sorted keys give the guesses in visiting order; the sorted values (row indices) leave the sort's buffer in the same pass.
+//
+// Block schedules (exact_plan.h): the filter sweep's cost per row block is the number of centroid groups its tiles must
+// visit, and that grows with the Elkan radius of the tile's outermost row.  The sorted keys still hold the quantised
+// distance, so the same pass writes a weight per 32-row tile (weight != null; a wave holds two tiles): its largest
+// distance field, scaled to 0..255, or 255 outright where the need set is wide whatever the distances say -- a row
+// without a guess (every group), or rows of two clusters (the union of two unrelated sets).  Integer only.
 __global__ void __launch_bounds__(WG) key_to_hint_kernel(const uint32_t* __restrict__ keys,
                                                          const uint32_t* __restrict__ vals, long n,
                                                          uint32_t* __restrict__ hint_sorted,
-                                                         uint32_t* __restrict__ order_out, int dbits) {
+                                                         uint32_t* __restrict__ order_out, int dbits, int k,
+                                                         unsigned char* __restrict__ weight) {
     const long i = (long)blockIdx.x * WG + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    if (i - lane >= n) return;                              // (the whole wave)
+    const uint32_t key = keys[i < n ? i : n - 1];           // (past the end: the last row again)
     if (i < n) {
-        hint_sorted[i] = keys[i] >> dbits;
+        hint_sorted[i] = key >> dbits;
         order_out[i] = vals[i];
+    }
+    if (!weight) return;
+    const uint32_t cluster = key >> dbits;
+    const uint32_t field = key & ((1u << dbits) - 1u);
+    int w = (int)(dbits >= 8 ? field >> (dbits - 8) : field << (8 - dbits));
+    if (cluster >= (uint32_t)k) w = exact_plan::SCHED_WEIGHT_MAX;
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) w = max(w, __shfl_xor(w, off));
+    const int first = __shfl((int)cluster, lane & 32), last = __shfl((int)cluster, (lane & 32) + 31);
+    if (first != last) w = exact_plan::SCHED_WEIGHT_MAX;
+    if ((lane & 31) == 0 && i < n) weight[i / 32] = (unsigned char)w;
+}
+
+// The class of block b of `nb` tiles: the top bits of the largest weight among its tiles.
+__device__ __forceinline__ int sched_block_class(const unsigned char* __restrict__ weight, long tiles, long b, int nb) {
+    int w = 0;
+    for (int t = 0; t < nb; t++)
+        if (b * nb + t < tiles) w = max(w, (int)weight[b * nb + t]);
+    return exact_plan::sched_class(w);
+}
+
+// Stable counting sort of the blocks by descending class, for the three block sizes at once (blockIdx.y: 1, 2, 4 tiles);
+// a workgroup owns SCHED_CHUNK consecutive blocks, eight rounds of 256.
+//   sched_hist_kernel    hist[size][chunk][class] = blocks of the class in the chunk
+//   sched_scan_kernel    ... -> where the chunk's blocks of the class start in the table (one workgroup per size)
+//   sched_scatter_kernel table[start + rank within the chunk] = block
+__global__ void __launch_bounds__(WG) sched_hist_kernel(const unsigned char* __restrict__ weight, long tiles, long chunks,
+                                                        uint32_t* __restrict__ hist) {
+    constexpr int NC = exact_plan::SCHED_CLASSES;
+    __shared__ unsigned cnt[NC];
+    const int nb = 1 << blockIdx.y;
+    const long blocks = (tiles + nb - 1) / nb;
+    const long base = (long)blockIdx.x * exact_plan::SCHED_CHUNK;
+    if (base >= blocks) return;
+    if (threadIdx.x < NC) cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    for (int r = 0; r < exact_plan::SCHED_CHUNK / WG; r++) {
+        const long b = base + r * WG + threadIdx.x;
+        if (b < blocks) atomicAdd(&cnt[sched_block_class(weight, tiles, b, nb)], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < NC) hist[((size_t)blockIdx.y * chunks + blockIdx.x) * NC + threadIdx.x] = cnt[threadIdx.x];
+}
+
+// (the counts pass through LDS in pieces of SCAN_PIECE chunks, so that the serial part never waits for global memory:
+// a Lloyd-sized order has 32 chunks, one piece)
+constexpr int SCAN_PIECE = 128;
+__global__ void __launch_bounds__(WG) sched_scan_kernel(long tiles, long chunks, uint32_t* __restrict__ hist) {
+    constexpr int NC = exact_plan::SCHED_CLASSES;
+    __shared__ unsigned piece[SCAN_PIECE * NC], run[NC], start[NC];
+    const int nb = 1 << blockIdx.x;
+    const long blocks = (tiles + nb - 1) / nb;
+    const long used = (blocks + exact_plan::SCHED_CHUNK - 1) / exact_plan::SCHED_CHUNK;   // chunks of this block size
+    uint32_t* h = hist + (size_t)blockIdx.x * chunks * NC;
+    const int t = threadIdx.x;
+    // pass 0: counts -> exclusive sums within the class, chunks ascending; then the classes, descending;
+    // pass 1: + where the class starts
+    for (int pass = 0; pass < 2; pass++) {
+        if (t < NC) run[t] = 0u;
+        for (long p0 = 0; p0 < used; p0 += SCAN_PIECE) {
+            const int m = (int)min((long)SCAN_PIECE, used - p0) * NC;
+            __syncthreads();
+            for (int e = t; e < m; e += WG) piece[e] = h[p0 * NC + e];
+            __syncthreads();
+            if (t < NC) {
+                if (pass == 0) {
+                    unsigned r = run[t];
+                    for (int e = t; e < m; e += NC) {
+                        const unsigned v = piece[e];
+                        piece[e] = r;
+                        r += v;
+                    }
+                    run[t] = r;
+                } else {
+                    for (int e = t; e < m; e += NC) piece[e] += start[t];
+                }
+            }
+            __syncthreads();
+            for (int e = t; e < m; e += WG) h[p0 * NC + e] = piece[e];
+        }
+        __syncthreads();
+        if (pass == 0 && t == 0) {
+            unsigned r = 0;
+            for (int q = NC - 1; q >= 0; q--) {
+                start[q] = r;
+                r += run[q];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(WG) sched_scatter_kernel(const unsigned char* __restrict__ weight, long tiles, long chunks,
+                                                           const uint32_t* __restrict__ hist, uint32_t* __restrict__ table0,
+                                                           uint32_t* __restrict__ table1, uint32_t* __restrict__ table2) {
+    constexpr int NC = exact_plan::SCHED_CLASSES;
+    constexpr int NW = WG / 64;
+    __shared__ unsigned next[NC], wave_cnt[NW][NC];
+    const int nb = 1 << blockIdx.y;
+    const long blocks = (tiles + nb - 1) / nb;
+    const long base = (long)blockIdx.x * exact_plan::SCHED_CHUNK;
+    if (base >= blocks) return;
+    uint32_t* table = blockIdx.y == 0 ? table0 : blockIdx.y == 1 ? table1 : table2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x < NC) next[threadIdx.x] = hist[((size_t)blockIdx.y * chunks + blockIdx.x) * NC + threadIdx.x];
+    for (int r = 0; r < exact_plan::SCHED_CHUNK / WG; r++) {
+        const long b = base + r * WG + threadIdx.x;
+        const int cls = b < blocks ? sched_block_class(weight, tiles, b, nb) : -1;
+        unsigned below = 0;   // blocks of my class on lower lanes of my wave
+        for (int q = 0; q < NC; q++) {
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(cls == q);
+            if (cls == q) below = (unsigned)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+            if (lane == 0) wave_cnt[wave][q] = (unsigned)__builtin_popcountll(m);
+        }
+        __syncthreads();   // (also: next[] of the round before)
+        if (cls >= 0) {
+            unsigned at = next[cls] + below;
+            for (int w = 0; w < wave; w++) at += wave_cnt[w][cls];
+            if (at < (unsigned long)blocks) table[at] = (uint32_t)b;   // (always, by the histogram: no write past the table)
+        }
+        __syncthreads();
+        if (threadIdx.x < NC)
+            for (int w = 0; w < NW; w++) next[threadIdx.x] += wave_cnt[w][threadIdx.x];
+        __syncthreads();   // (wave_cnt is rewritten by the next round)
     }
 }
 
@@ -354,6 +488,60 @@ int at_prune_prepass(at_ctx* ctx, const at_exact_call& call, int64_t n, const ui
     return AT_OK;
 }
 
+// The block schedules of the order being made (at_internal.h: at_block_sched_state).  begin: the half of the workspace
+// this call writes, claimed and entered on the stream of the visiting order; *weight = where key_to_hint_kernel puts the
+// tile weights.  finish: the counting sort of the three tables, three small launches behind that kernel.
+// The visiting order sits on the critical path of a Lloyd iteration (the next sweep waits for it), so what is queued
+// behind the sort costs the step time: DESIGN.md section 5.0f lists the forms that were tried and cost more than this one
+// (the sort on a stream of the context's own, one workgroup per table, class counts by atomics in key_to_hint_kernel).
+// begin can stall that chain twice, both rarely: at_ws drains the device when the slot has to grow (until it has reached
+// the largest n of the run), and a call whose n differs from the last one's enters both guards and drops both tags --
+// a run that alternates Lloyd-sized and tokenise-sized orders lays the slot out anew at every switch (a wait only if a
+// sweep on another stream still reads a half, which the Lloyd loop's joins exclude).
+static int block_schedules_begin(at_ctx* ctx, int64_t n, const uint32_t* order_out, hipStream_t stream, unsigned char** weight) {
+    at_block_sched_state& s = ctx->sched;
+    const exact_plan::SchedLayout l = exact_plan::sched_layout(n);
+    const int half = (int)(s.calls & 1u);
+    if (s.layout_n != n) {   // the halves move: nobody may still be reading either, and neither holds a table any more
+        for (int h = 0; h < 2; h++) {
+            const int rc = at_guard_enter(&s.guard[h], stream);
+            if (rc) return rc;
+            s.tag[h].valid = 0;
+        }
+        s.layout_n = 0;
+    }
+    s.tag[half].valid = 0;
+    if (s.tag[half ^ 1].order == order_out) s.tag[half ^ 1].valid = 0;   // (the buffer holds another order now)
+    unsigned char* slot = static_cast<unsigned char*>(at_ws(ctx, WS_BLOCK_SCHED, 2 * l.bytes, stream));
+    if (!slot) return AT_E_NOMEM;
+    s.layout_n = n;
+    const int rc = at_guard_enter(&s.guard[half], stream);   // a sweep on another stream may still read this half
+    if (rc) return rc;
+    *weight = slot + (size_t)half * l.bytes + l.weight_off;
+    return AT_OK;
+}
+
+static int block_schedules_finish(at_ctx* ctx, int64_t n, const uint32_t* order_out, hipStream_t stream) {
+    at_block_sched_state& s = ctx->sched;
+    const exact_plan::SchedLayout l = exact_plan::sched_layout(n);
+    const int half = (int)(s.calls & 1u);
+    unsigned char* base = static_cast<unsigned char*>(ctx->ws[WS_BLOCK_SCHED]) + (size_t)half * l.bytes;
+    const unsigned char* weight = base + l.weight_off;
+    uint32_t* hist = reinterpret_cast<uint32_t*>(base + l.hist_off);
+    uint32_t* table[3];
+    for (int t = 0; t < 3; t++) table[t] = reinterpret_cast<uint32_t*>(base + l.table_off[t]);
+    const dim3 grid((unsigned)l.chunks, 3);
+    AT_LAUNCH(sched_hist_kernel, grid, dim3(WG), 0, stream, weight, (long)l.tiles, (long)l.chunks, hist);
+    AT_LAUNCH(sched_scan_kernel, dim3(3), dim3(WG), 0, stream, (long)l.tiles, (long)l.chunks, hist);
+    AT_LAUNCH(sched_scatter_kernel, grid, dim3(WG), 0, stream, weight, (long)l.tiles, (long)l.chunks, hist, table[0], table[1],
+              table[2]);
+    const int rc = at_guard_leave(&s.guard[half], stream);
+    if (rc) return rc;
+    s.tag[half] = exact_plan::SchedTag{order_out, n, 1};
+    s.calls++;
+    return AT_OK;
+}
+
 extern "C" {
 
 int at_group_min_dist_f32(at_ctx* ctx, const float* c, int k, int d, const int32_t* cperm, int ng,
@@ -433,8 +621,15 @@ int at_visit_order_f32(at_ctx* ctx, const int64_t* ids, const float* dis, int64_
     rocprim::double_buffer<uint32_t> kb(keys_a, keys_b);
     rocprim::double_buffer<uint32_t> vb(vals_a, vals_b);
     { const int rc = at_sort_pairs(ctx, WS_VISIT_TMP, kb, vb, (size_t)n, 0, bits, stream); if (rc != AT_OK) return rc; }
+    // (switch block_sched: 0 = no tables are made, the sweeps start their blocks in visiting order)
+    unsigned char* weight = nullptr;
+    if (ctx->dbg.block_sched != 0) {
+        const int rc = block_schedules_begin(ctx, n, order_out, stream, &weight);
+        if (rc != AT_OK) return rc;
+    }
     AT_LAUNCH(key_to_hint_kernel, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, stream, kb.current(),
-                       vb.current(), (long)n, hint_sorted_out, order_out, dbits);
+                       vb.current(), (long)n, hint_sorted_out, order_out, dbits, k, weight);
+    if (weight) return block_schedules_finish(ctx, n, order_out, stream);
     return AT_OK;
 }
 

@@ -8,7 +8,7 @@
  *                                 from the environment again; names:
  *                                   assign_variant filter_fused filter_sync prune_kernel prune_nb filter_screen
  *                                   filter_nb filter_wps2 dmin_kernel resample_simple accum_buckets filter_stats visit_bits
- *                                   filter_timing logmel_fallback ap_ws_mb strict_errors
+ *                                   filter_timing logmel_fallback ap_ws_mb block_sched strict_errors
  *                                 (logmel_fallback = 1 is the one switch that does NOT keep the bits: the even n_fft that
  *                                 are not powers of two all take the Bluestein form of the transform, so that it can be
  *                                 held against the mixed-radix form at the sizes that have both; same tolerance)
@@ -22,6 +22,8 @@
  *                                 strict_errors (process-wide, also AT_STRICT_ERRORS): a HIP error found pending in the
  *                                 calling thread in front of one of the library's launches fails the call ("stale error
  *                                 from an earlier call") instead of being consumed and counted
+ *                                 block_sched = 0: at_visit_order_f32 makes no block schedules and the exact filter sweeps
+ *                                 start their row blocks in visiting order (default 1: widest need sets first);
  *   at_diag_errors                what the library met and did not treat as its own failure: errors pending in front of a
  *                                 launch (somebody's earlier call failed and nobody consumed the error) and failures it
  *                                 tolerates by design; counts, last codes and source positions.  No device work.
@@ -35,6 +37,15 @@
  *                                 of row i's winner and its gap to the runner-up; *listed = rows it would hand on.
  *   at_prune_peek                 test hook: bd [n] and mask [ceil(n/32)][ceil(ng/32)] as the preceding at_prune_mask_f32
  *                                 (same n, ng, same stream) left them in the workspace, copied to DEVICE buffers.
+ *   at_block_sched_install        test hook: a caller-made block schedule (HOST array) for the exact filter sweeps of exactly
+ *                                 `blocks` row blocks, until blocks = 0 removes it; refused unless it is a permutation of
+ *                                 [0, blocks).  Waits for the device.
+ *   at_block_sched_peek           test hook: the table of blocks of `tiles` 32-row tiles (1, 2, 4) that at_visit_order_f32
+ *                                 made beside `order` (its order_out, n rows), and the tile weights (bytes, may be NULL),
+ *                                 copied to DEVICE buffers in stream order; *found = 0 when no table carries that tag.
+ *   at_block_sched_last           what the context's last filter sweep started its blocks by: 0 visiting order, 1 a table
+ *                                 made beside its order, 2 the installed schedule; its tiles per block and block count.
+ *   at_block_sched_limits         the row counts up to which an exact d = 64 sweep runs one / two tiles per wave.
  *   at_waccum_limits              the member-list lengths at which at_centroid_accum_weighted_f32 changes its path: rows
  *                                 per register set of the one-wave kernel (lanes with 1 or 2 features / with 4), the
  *                                 longest list that kernel walks (longer ones go to the feature-sliced kernel) and the
@@ -62,6 +73,11 @@ int at_filter_probe_f32(at_ctx* ctx, const float* x, int64_t n, int d, const flo
                         const uint32_t* order, const uint32_t* hint_sorted, const int32_t* cperm, int ng,
                         const float* dmin, int64_t* ids, float* approx, int64_t* listed, void* stream);
 int at_prune_peek(at_ctx* ctx, int64_t n, int ng, float* bd_out, uint32_t* mask_out, void* stream);
+int at_block_sched_install(at_ctx* ctx, const uint32_t* sched_host, int64_t blocks);
+int at_block_sched_peek(at_ctx* ctx, const uint32_t* order, int64_t n, int tiles, uint32_t* table_out,
+                        unsigned char* weight_out, int* found, void* stream);
+int at_block_sched_last(at_ctx* ctx, int* path, int* tiles, int64_t* blocks);
+int at_block_sched_limits(int64_t* one_tile_max_rows, int64_t* two_tile_max_rows);
 int at_waccum_limits(int* short_batch, int* short_batch_wide, int* long_list, int* ring_chunk);
 
 #ifdef __cplusplus
