@@ -688,6 +688,43 @@ class HipBackend(HostHelpers):
                                                  self._stream()))
         return out
 
+    def pq_search(self, x, codebooks, codes, k, want_dist=True):
+        """The k nearest stored codes of every query by asymmetric distance (at_pq_search_f32): x [n, d], codebooks
+        [M, ksub, d / M] (made float32, contiguous, on the device; 1 <= M <= 64, 1 <= ksub <= 256), codes [ntotal, M]
+        uint8 (host or device), 1 <= k <= 128 -> (ids [n, k] int64, dist [n, k] float32 or None), ascending (dis, id).
+        dis is the sum over m, ascending, of the direct-form distance between sub-vector m of the query and word
+        codes[r, m] of codebook m; rows with dis < +inf are listed, the slots left over are (-1, +inf); a row with a
+        code >= ksub is never listed.  k < 1 raises RuntimeError.  Nothing is read back."""
+        k = int(k)
+        if k < 1:
+            raise RuntimeError(f"pq_search: k must be at least 1, got {k}")
+        x, cb = self._f32(x), self._f32(codebooks)
+        if isinstance(codes, np.ndarray):
+            codes = torch.from_numpy(np.ascontiguousarray(codes))
+        assert x.dim() == 2 and cb.dim() == 3, "pq_search: x must be [n, d] and codebooks [M, ksub, dsub]"
+        assert codes.dtype == torch.uint8 and codes.dim() == 2 and codes.shape[1] == cb.shape[0], \
+            f"pq_search: codes must be uint8 [ntotal, {cb.shape[0]}]"
+        codes = codes.to(self.device).contiguous()
+        n, d = x.shape
+        M, ksub, dsub = cb.shape
+        if M * dsub != d:
+            raise ValueError(f"pq_search: codebooks {tuple(cb.shape)} do not cut rows of {d} features")
+        ids = self.empty((n, k), torch.int64)
+        dist = self.empty((n, k), torch.float32) if want_dist else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_pq_search_f32(self.ctx.handle, _ptr(x), n, d, M, ksub, _ptr(cb), _ptr(codes),
+                                                 codes.shape[0], k, _ptr(ids), _ptr(dist), self._stream()))
+        return ids, dist
+
+    @staticmethod
+    def pq_search_limits(M, ntotal, k) -> dict:
+        """include/at_debug.h, at_pq_search_limits: queries per workgroup, database rows per slab and queries per chunk
+        of a pq_search() call of that shape (for the tests that sit on those seams)."""
+        qb, slab, chunk = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+        _lib.check(_lib.load().at_pq_search_limits(ctypes.byref(qb), ctypes.byref(slab), ctypes.byref(chunk), int(M),
+                                                   int(ntotal), int(k)))
+        return {"queries_per_block": int(qb.value), "slab_rows": int(slab.value), "queries_per_chunk": int(chunk.value)}
+
     def rq_encode(self, x, codebooks, want_dist=False, want_residual=False):
         """Greedy residual-quantiser codes (at_rq_encode_f32): x [n, d], codebooks [M, ksub, d] (made float32,
         contiguous, on the device; 1 <= ksub <= 256) -> (codes [n, M] uint8, dist [n, M] float32 or None, residual

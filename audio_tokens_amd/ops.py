@@ -20,6 +20,8 @@
         (processors/spectrogram_generator.py:99)
     get_spectrogram + get_sequence                        ->  AudioTokenizer
         (tools/manual_tester.py: audio -> tokens against a trained vocabulary)
+    faiss.ProductQuantizer, faiss.IndexPQ                 ->  ProductQuantizer, IndexPQ
+        (not used by the reference: M code bytes per frame, and the search over them)
     torchaudio.transforms.MFCC, ComputeDeltas             ->  MFCC, ComputeDeltas
         (not used by the reference: the 13 + delta + delta-delta features of HTK / Kaldi-style tokenisers)
 
@@ -48,7 +50,8 @@ from .backend import default_backend
 __all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "IndexFlatIP", "normalize_rows", "silhouette_samples",
            "silhouette_score", "average_precision", "mean_average_precision", "roc_auc", "mean_roc_auc",
            "roc_auc_score", "d_prime", "f1_score", "hamming_loss", "classification_metrics", "load_flac",
-           "load_flac_batch", "AudioTokenizer", "ProductQuantizer", "ResidualQuantizer", "MFCC", "ComputeDeltas"]
+           "load_flac_batch", "AudioTokenizer", "ProductQuantizer", "ResidualQuantizer", "MFCC", "ComputeDeltas",
+           "IndexPQ"]
 
 
 def _is_host(x) -> bool:
@@ -1110,6 +1113,110 @@ class ProductQuantizer:
             idx = codes.to(torch.int64)
             out = torch.cat([cb[m][idx[:, m]] for m in range(self.M)], 1).contiguous()
         return be.to_host(out) if host else out
+
+
+class IndexPQ:
+    """faiss.IndexPQ(d, M, nbits=8) with train / add / search(x, k) / reconstruct / reset / ntotal: the frames are kept as
+    the M code bytes of `pq`, an ops.ProductQuantizer built from the constructor's arguments (same errors for d % M and
+    nbits), and searched without being decoded (not used by the reference).
+
+    add(x) appends pq.compute_codes(x) on the device (check_finite passes through; the encoder's error is raised
+    before anything is appended); add_codes(codes) appends a ready uint8 [n, M] array, host or device; `codes` is the
+    device tensor [ntotal, M]; reset() drops the codes and keeps the codebooks.
+
+    search(x, k) returns (D, I), [n, k] float32 / int64: numpy for host input, device tensors (on the caller's current
+    stream) for device input.  The distance of query i to stored row r is the asymmetric one of faiss's default
+    ST_PQ search -- the table T[i, m, j] = sum_f (x[i, m*dsub + f] - codebook[m, j, f])^2, always in the direct form (one
+    fp32 subtraction, an ascending fmaf chain from +0), then T[i, 0, codes[r, 0]] + T[i, 1, codes[r, 1]] + ... added in
+    ascending m, one fp32 addition each -- recalled from faiss, not verified against its output.  Row i lists the k
+    smallest (dis, r) in lexicographic order, only rows with dis < +inf (NaN never is); the slots left over (ntotal <
+    k, an empty index, a NaN or Inf in the query, overflow) hold I = -1, D = +inf: IndexFlatL2.search's conventions,
+    its deviation from faiss's FLT_MAX included.  k < 1 raises RuntimeError, as faiss does; k > 128 and M > 64 raise
+    NotImplementedError (the kernel keeps a query's tables and candidates in LDS; there is no path behind either
+    limit), and so does a backend without pq_search(): torch arithmetic cannot restate the fmaf chain, so there is no
+    composed route.  reconstruct_n(i0, n) / reconstruct(i) return pq.decode of the stored codes (numpy)."""
+
+    MAX_M, MAX_K = 64, 128
+
+    def __init__(self, d, M, nbits=8, niter=25, seed=1234, max_points_per_centroid=256, verbose=False, backend=None):
+        self.pq = ProductQuantizer(d, M, nbits=nbits, niter=niter, seed=seed,
+                                   max_points_per_centroid=max_points_per_centroid, verbose=verbose, backend=backend)
+        if self.pq.M > self.MAX_M:
+            raise NotImplementedError(f"IndexPQ: M = {self.pq.M} (at most {self.MAX_M} sub-quantisers are implemented)")
+        self.backend = self.pq.backend
+        if not hasattr(self.backend, "pq_search"):
+            raise NotImplementedError("IndexPQ needs a backend with pq_search()")
+        self.d, self.M = self.pq.d, self.pq.M
+        self._codes = None
+
+    @property
+    def is_trained(self) -> bool:
+        return self.pq.is_trained
+
+    @property
+    def ntotal(self) -> int:
+        return 0 if self._codes is None else int(self._codes.shape[0])
+
+    @property
+    def codes(self):
+        """The stored codes, a uint8 device tensor [ntotal, M]."""
+        if self._codes is None:
+            return self.backend.empty((0, self.M), torch.uint8)
+        return self._codes
+
+    def train(self, x) -> None:
+        self.pq.train(x)
+
+    def reset(self) -> None:
+        self._codes = None
+
+    def _append(self, codes) -> None:
+        if isinstance(codes, np.ndarray):   # (a backend whose device is the host answers with numpy)
+            codes = torch.from_numpy(np.ascontiguousarray(codes))
+        assert codes.dim() == 2 and codes.shape[1] == self.M and codes.dtype == torch.uint8, \
+            f"IndexPQ: expected uint8 codes [n, {self.M}]"
+        codes = codes.to(self.backend.device).contiguous()
+        self._codes = codes.clone() if self._codes is None else torch.cat([self._codes, codes], 0)
+
+    def add(self, x, check_finite=True) -> None:
+        if not self.is_trained:
+            raise RuntimeError("IndexPQ.add: the index is not trained (call train() or pq.set_centroids())")
+        x = self.pq._rows(x, "IndexPQ.add")   # (on the device: compute_codes then answers with a device tensor)
+        self._append(self.pq.compute_codes(x, check_finite=check_finite))
+
+    def add_codes(self, codes) -> None:
+        self._append(codes)
+
+    def search(self, x, k=1):
+        k = int(k)
+        if k < 1:
+            raise RuntimeError(f"IndexPQ.search: k must be at least 1, got {k}")
+        if k > self.MAX_K:
+            raise NotImplementedError(f"IndexPQ.search: k = {k} (at most {self.MAX_K} neighbours are implemented)")
+        if not self.is_trained:
+            raise RuntimeError("IndexPQ.search: the index is not trained (call train() or pq.set_centroids())")
+        be = self.backend
+        host = _is_host(x)
+        x = self.pq._rows(x, "IndexPQ.search")
+        if self._codes is None:
+            D = torch.full((x.shape[0], k), float("inf"), device=be.device)
+            I = torch.full((x.shape[0], k), -1, dtype=torch.int64, device=be.device)
+        else:
+            I, D = be.pq_search(x, self.pq.centroids_device, self._codes, k)
+        return (be.to_host(D), be.to_host(I)) if host else (D, I)
+
+    def reconstruct_n(self, i0=0, n=-1):
+        """float32 numpy [n, d]: the decoded rows i0 .. i0 + n - 1 (n = -1: to the end)."""
+        i0, n = int(i0), int(n)
+        if n < 0:
+            n = self.ntotal - i0
+        if i0 < 0 or n < 0 or i0 + n > self.ntotal:
+            raise RuntimeError(f"IndexPQ.reconstruct_n: rows {i0} .. {i0 + n} of {self.ntotal}")
+        out = self.pq.decode(self.codes[i0:i0 + n])
+        return out if isinstance(out, np.ndarray) else self.backend.to_host(out)
+
+    def reconstruct(self, i):
+        return self.reconstruct_n(i, 1)[0]
 
 
 class ResidualQuantizer:

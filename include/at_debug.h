@@ -50,6 +50,10 @@
  *                                 per register set of the one-wave kernel (lanes with 1 or 2 features / with 4), the
  *                                 longest list that kernel walks (longer ones go to the feature-sliced kernel) and the
  *                                 members per buffer of that kernel's LDS ring (NULL skips a field).  No device work.
+ *   at_pq_search_limits           the seams of at_pq_search_f32 for a call with M sub-spaces, ntotal database rows and k
+ *                                 places: queries per workgroup (4 up to M = 32, 2 above), database rows per slab, and
+ *                                 the queries whose lists fill the workspace budget -- a call with more takes them in
+ *                                 chunks of that many (NULL skips a field).  No device work.
  */
 #ifndef AUDIO_TOKENS_AMD_DEBUG_H
 #define AUDIO_TOKENS_AMD_DEBUG_H
@@ -79,6 +83,7 @@ int at_block_sched_peek(at_ctx* ctx, const uint32_t* order, int64_t n, int tiles
 int at_block_sched_last(at_ctx* ctx, int* path, int* tiles, int64_t* blocks);
 int at_block_sched_limits(int64_t* one_tile_max_rows, int64_t* two_tile_max_rows);
 int at_waccum_limits(int* short_batch, int* short_batch_wide, int* long_list, int* ring_chunk);
+int at_pq_search_limits(int* queries_per_block, int* slab_rows, int64_t* queries_per_chunk, int M, int64_t ntotal, int k);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@
  *   faiss.IndexFlatL2(d).search(x, k), k >= 2 (not used by the reference)  at_knn_f32
  *   faiss.IndexFlatIP(d).search(x, 1), Kmeans(spherical=True) (likewise)   at_assign_ip_f32, at_renorm_rows_f32
  *   faiss.ProductQuantizer(d, M, 8).compute_codes(x) / .decode(codes) (likewise)  at_pq_encode_f32, at_pq_decode_f32
+ *   faiss.IndexPQ(d, M, 8).search(x, k) over stored codes (likewise; the library's own contract)  at_pq_search_f32
  *   greedy residual quantiser (RVQ, beam 1; the library's own contract)    at_rq_encode_f32, at_rq_decode_f32
  *   beam-search residual quantiser (beam 1 .. 32; the library's own contract)  at_rq_beam_step_f32, at_rq_beam_encode_f32
  *   torchaudio.transforms.MFCC / ComputeDeltas on log-mel rows (likewise)  at_mfcc_f32, at_deltas_f32,
@@ -554,6 +555,29 @@ int at_pq_encode_f32(at_ctx* ctx, const float* x, int64_t n, int d, int M, int k
  * dsub % 4 == 0 and codebooks / out are 16-byte aligned, one float per thread otherwise.  No workspace. */
 int at_pq_decode_f32(at_ctx* ctx, const uint8_t* codes, int64_t n, int d, int M, int ksub, const float* codebooks,
                      float* out, void* stream);
+
+/* Product quantiser, asymmetric-distance search over stored codes (faiss IndexPQ::search in its default ST_PQ mode,
+ * recalled, NOT verified against faiss output: the contract is the library's own).  Query row x[i] gets the table
+ *   T[i][m][j] = sum_f (x[i][m * dsub + f] - codebooks[m][j][f])^2, df = x - c one fp32 subtraction, acc = fmaf(df, df,
+ *   acc) from +0 over f ascending -- the direct form whatever n is (at_assign_f32's arithmetic for calls of n < 20 rows);
+ * database row r the distance dis(i, r) = T[i][0][codes[r][0]] + T[i][1][codes[r][1]] + ..., one fp32 addition per
+ * step in ascending m, starting from the m = 0 entry.  Row r is listed for query i only if dis(i, r) < +inf (a NaN never
+ * is); row i of the result holds the k smallest (dis, r), lexicographic and ascending, the lower id first on equal
+ * distances; the places left over (ntotal < k, a NaN or Inf in the query, overflow) hold ids = -1, dist = +inf:
+ * at_knn_f32's conventions.  No flag word: a non-finite query is not an error.  A stored code >= ksub (possible only
+ * with ksub < 256) makes that database row unlisted for every query and is never used as an index.
+ *   x: [n][d] fp32; codebooks: [M][ksub][d/M] fp32; codes: uint8 [ntotal][M]; d % M == 0, 1 <= M <= 64, 1 <= ksub <= 256,
+ *   1 <= k <= 128, 0 <= ntotal < 2^31, n >= 0 (n == 0 is a no-op that touches no pointer; ntotal == 0 fills the outputs
+ *   and does not touch codes); ids: int64 [n][k]; dist_or_null: float [n][k].  Anything else is AT_E_INVALID: there is
+ *   no general path behind M <= 64 (the tables of a workgroup's queries stay in LDS) or k <= 128 (so do its candidates).
+ * Two launches per chunk of queries (csrc/pq_search.hip): the scan -- a workgroup builds the tables of 4 queries (2 for
+ * M > 32) in LDS, streams a slab of 65 536 code rows once with 16-, 8-, 4- or 1-byte loads as M and the pointer allow,
+ * and keeps the k smallest keys per query -- and the merge of the slabs' lists.  No [n][ntotal] matrix exists anywhere;
+ * the lists (8 bytes per query, slab and place) live in the context, a chunk of queries within 256 MiB (and 2^24 - 4 queries).  No host
+ * synchronisation, no device-to-host copy; a call on another stream than the context's previous at_pq_search_f32 waits
+ * for it. */
+int at_pq_search_f32(at_ctx* ctx, const float* x, int64_t n, int d, int M, int ksub, const float* codebooks,
+                     const uint8_t* codes, int64_t ntotal, int k, int64_t* ids, float* dist_or_null, void* stream);
 
 /* Residual quantiser (RVQ), greedy encoder: beam width 1, M dependent stages.  r_0 = x; for m = 0 .. M-1 in order,
  * (codes[i][m], dist[i][m]) is at_assign_f32's answer for the rows r_m against codebooks[m] ([ksub][d]), bit for bit:
