@@ -87,12 +87,16 @@ __device__ __forceinline__ float sqnorm16(const float* xrow, int d) {
     return xn;
 }
 
-// chunk ch of a row of d features (d % 4 == 0, zero past d) as the B operand of half-wave h: xv[i] = feature 2 i + h
-__device__ __forceinline__ void load_x_chunk(const float* xrow, int ch, int d, int h, float (&xv)[DC / 2]) {
+// chunk ch of a row of d features (d % 4 == 0, `pad` past d) as the B operand of half-wave h: xv[i] = feature 2 i + h.
+// pad = +0 is enough wherever the sign of a zero product is never seen (the L2 routes: fma(-2, +-0, xn + cn) is the
+// same number); ip.hip reports the product itself and pads with -0: against the image's +0 a pad step then adds -0,
+// which leaves every accumulator as it is, a -0 included (+0 would turn it into +0).
+__device__ __forceinline__ void load_x_chunk(const float* xrow, int ch, int d, int h, float (&xv)[DC / 2],
+                                             float pad = 0.0f) {
 #pragma unroll
     for (int q = 0; q < DC / 8; q++) {
         const int f = ch * DC + 8 * q;
-        f32x4 u = {0, 0, 0, 0}, v = {0, 0, 0, 0};
+        f32x4 u = {pad, pad, pad, pad}, v = {pad, pad, pad, pad};
         if (f < d) u = *reinterpret_cast<const f32x4*>(xrow + f);
         if (f + 4 < d) v = *reinterpret_cast<const f32x4*>(xrow + f + 4);
         xv[4 * q + 0] = h ? u[1] : u[0];
@@ -185,10 +189,11 @@ struct Sweep {
         __syncthreads();
     }
 
-    // NCH > 0: xr holds the row's chunks; NCH = 0: xr[0] is reloaded from xrow (d features) for every piece
+    // NCH > 0: xr holds the row's chunks; NCH = 0: xr[0] is reloaded from xrow (d features, xpad behind them) for
+    // every piece
     template <typename F>
     __device__ __forceinline__ void run(int t0, int t1, f32x16 (&acc)[NA], float (&xr)[NCH > 0 ? NCH : 1][DC / 2],
-                                        const float* xrow, int d, F&& done) const {
+                                        const float* xrow, int d, F&& done, float xpad = 0.0f) const {
         if constexpr (NCH > 0) {
             for (int ct = t0; ct < t1; ct++) {   // (written out: a chunk index must be a constant here)
                 stage(ct * NCH, ct, 0, acc, xr[0], done);
@@ -197,7 +202,7 @@ struct Sweep {
         } else {
             int ct = t0, ch = 0;
             for (int s = t0 * nch; s < t1 * nch; s++) {
-                load_x_chunk(xrow, ch, d, h, xr[0]);
+                load_x_chunk(xrow, ch, d, h, xr[0], xpad);
                 stage(s, ct, ch, acc, xr[0], done);
                 if (++ch == nch) { ch = 0; ct++; }
             }

@@ -3,7 +3,8 @@
 //
 // Arithmetic contract of the search:
 //   ip(i,j) = fmaf chain over the feature index, ascending, from +0 (v_mfma_f32_32x32x2_f32): the ip of at_assign_f32,
-//             at every n (faiss's small-batch form is the same sum);
+//             at every n (faiss's small-batch form is the same sum); a zero result keeps the sign the chain gives it (a
+//             negative product that underflows rounds to -0), at every d;
 //   centroid j is listed for row i iff ip(i,j) > -inf (a NaN product never is, +inf is);
 //   ids[i] = the lowest j among the listed centroids with the largest ip(i,j), ip[i] = that product with its own bits;
 //   rows with nothing to list: ids = -1, ip = -inf.
@@ -79,7 +80,7 @@ ip_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const fl
                 }
             }
         }
-    });
+    }, -0.0f);   // the features behind d of a partial last chunk: a product of -0 keeps the chain's zero, sign included
 
     unsigned idx = cs::index_of(bcode, h);
     cs::merge_halves_max(best, idx);

@@ -520,7 +520,8 @@ int at_knn_f32(at_ctx* ctx, const float* x, int64_t n, int d, const float* c, in
  *   at every n (faiss's small-batch form is the same sum).  Centroid j is listed for row i iff ip(i,j) > -inf: a NaN
  *   product never is, +inf is.  ids[i] = the lowest j among the listed centroids with the largest ip(i,j); ip[i] = that
  *   product with its own bits.  Rows with nothing to list (NaN rows) get ids = -1, ip = -inf (faiss's heap would leave
- *   -FLT_MAX there).
+ *   -FLT_MAX there).  A product of zero keeps the sign the chain gives it, at every d: a negative term that underflows
+ *   rounds to -0, and -0 and +0 compare equal, so the sign never decides an id.
  *   x: [n][d] fp32; c: [k][d] fp32, 1 <= k <= 2^24; ids: int64 [n]; ip_or_null: float [n].  n == 0 is a no-op.
  * d % 4 == 0 on 16-byte aligned rows: one dense MFMA sweep (x in registers at d = 64 and 128, re-read per 64-feature
  * chunk otherwise); everything else: the same chain in scalar code.  Like at_assign_f32 the call keeps its centroid
