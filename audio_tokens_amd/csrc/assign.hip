@@ -11,7 +11,7 @@
 //   A centroid is a candidate only with dis < +inf (the strict '<' from +inf): a row none of whose distances is
 //   finite -- |x|^2 overflows from finite elements -- is (-1, +inf) on every route, whatever it was hinted; a
 //   centroid whose |c|^2 is +inf is never named.  The dense epilogue has this from its compare; the hinted and
-//   pruned sweeps, whose exact update breaks ties by index, from no_winner() where they store the answer.
+//   pruned sweeps, whose exact update breaks ties by index, from no_winner() where store_answer() writes the row.
 //
 // Data flow.  The centroid table is re-laid once per call into tiles of 32*NA centroids whose rows
 // are already in LDS order (k split even/odd per 8 features so that one ds_read_b128 feeds four
@@ -24,6 +24,13 @@
 // between the MFMAs of the next one, including across the tile boundary (the last accumulator of
 // a tile is carried into the next loop iteration).  HBM traffic: x once (4d B/row) + 12 B/row out;
 // the centroid image (k*d*4 B) is L2/Infinity-Cache resident.  Bound: fp32 MFMA (2*d*k flop/row).
+//
+// Layout of this file.  Five MFMA sweeps share one arithmetic: assign_mfma_kernel (dense, d = 64 / 128),
+// assign_mfma_hinted_kernel, assign_mfma_pruned_kernel (LDS-DMA) and assign_mfma_pruned_reg_kernel (register-staged),
+// assign_mfma_anyd_kernel (any d % 4 == 0).  Each step of that arithmetic is written once, above the kernels ("The
+// steps that the MFMA sweeps share"; the layout functions, the x chunk, the half-wave merge and the 1 KiB DMA come from
+// chunked_sweep.h), and a kernel body is its schedule: what it stages, when it prefetches, when it finishes an
+// accumulator.  Where a kernel keeps a step written out, a comment there says what the shared form cost it.
 #include <cstdlib>
 
 #include "at_internal.h"
@@ -42,6 +49,29 @@ __host__ __device__ constexpr int tile_floats(int dp, int na) { return tile_rows
 // Centroid image: tile t holds rows t*R .. t*R+R-1 (R = 32*na).  Row r, 16-byte chunk pc
 // (physical) holds logical chunk lc = pc ^ (r & 15); lc = 2q + h holds features 8q + {0,2,4,6} + h.
 // Features >= d and rows >= k are zero; |c|^2 of a row >= k is +inf so it can never win.
+//
+// The 16 bytes of physical slot pc of image row r, from centroid crow (nullptr: a pad row) and the features from f0 on:
+// the swizzle is an involution, so slot pc holds logical slot lc = cs::chunk_slot(r, pc >> 1, pc & 1).
+__device__ __forceinline__ f32x4 image_slot(const float* crow, int d, int f0, int r, int pc) {
+    const int lc = cs::chunk_slot(r, pc >> 1, pc & 1);
+    const int q = lc >> 1, h = lc & 1;
+    f32x4 v;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int f = f0 + 8 * q + 2 * u + h;
+        v[u] = (crow && f < d) ? crow[f] : 0.0f;
+    }
+    return v;
+}
+
+// |c|^2 as the ascending fmaf chain; +inf for a pad row
+__device__ __forceinline__ float image_norm(const float* crow, int d) {
+    if (!crow) return __builtin_inff();
+    float nrm = 0.0f;
+    for (int f = 0; f < d; f++) nrm = __builtin_fmaf(crow[f], crow[f], nrm);
+    return nrm;
+}
+
 __global__ void __launch_bounds__(WG) prep_centroids_kernel(const float* __restrict__ c, int k, int d,
                                                             int dp, int na, float* __restrict__ img) {
     const int t = blockIdx.x;
@@ -50,28 +80,13 @@ __global__ void __launch_bounds__(WG) prep_centroids_kernel(const float* __restr
     const int chunks_per_row = dp / 4;
     for (int e = threadIdx.x; e < R * chunks_per_row; e += WG) {
         const int r = e / chunks_per_row, pc = e % chunks_per_row;
-        const int lc = pc ^ (r & 15);
-        const int q = lc >> 1, h = lc & 1;
         const int row = t * R + r;
-        f32x4 v;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int f = 8 * q + 2 * u + h;
-            v[u] = (row < k && f < d) ? c[(size_t)row * d + f] : 0.0f;
-        }
-        *reinterpret_cast<f32x4*>(out + (size_t)r * dp + pc * 4) = v;
+        *reinterpret_cast<f32x4*>(out + (size_t)r * dp + pc * 4) =
+            image_slot(row < k ? c + (size_t)row * d : nullptr, d, 0, r, pc);
     }
     for (int r = threadIdx.x; r < CN_PAD; r += WG) {
         const int row = t * R + r;
-        float nrm = __builtin_inff();
-        if (r < R && row < k) {
-            nrm = 0.0f;
-            for (int f = 0; f < d; f++) {
-                const float v = c[(size_t)row * d + f];
-                nrm = __builtin_fmaf(v, v, nrm);
-            }
-        }
-        out[R * dp + r] = nrm;
+        out[R * dp + r] = image_norm(r < R && row < k ? c + (size_t)row * d : nullptr, d);
     }
 }
 
@@ -93,15 +108,18 @@ __device__ __forceinline__ void argmin_step(float& bd, unsigned& br, float dis) 
         : "vcc");
 }
 
+// (xn + cn) - 2*ip of accumulator register r, the contract's distance before its clamp: one rounding for the add, one
+// for the fma.  cnv: the lane's 16 norms (load_norms16).
+__device__ __forceinline__ float dist_unclamped(const f32x16& acc, int r, float xn, const f32x4 (&cnv)[4]) {
+    return __builtin_fmaf(-2.0f, acc[r], xn + cnv[r >> 2][r & 3]);
+}
+
 // dis = max(0, (xn + cn) - 2*ip) for accumulator register R, then the arg-min step.
 template <int R>
 __device__ __forceinline__ void epilogue_from(float& bd, unsigned& br, const f32x16& acc, float xn,
                                               const f32x4 (&cnv)[4]) {
     if constexpr (R < 16) {
-        const float t = xn + cnv[R >> 2][R & 3];
-        float dis = __builtin_fmaf(-2.0f, acc[R], t);
-        dis = __builtin_fmaxf(dis, 0.0f);
-        argmin_step<R>(bd, br, dis);
+        argmin_step<R>(bd, br, __builtin_fmaxf(dist_unclamped(acc, R, xn, cnv), 0.0f));
         epilogue_from<R + 1>(bd, br, acc, xn, cnv);
     }
 }
@@ -131,7 +149,7 @@ __device__ __forceinline__ void epilogue16_spec(float& bestd, unsigned& bestc, c
                                                 const f32x4 (&cnv)[4], unsigned codebase) {
     float dis[16];
 #pragma unroll
-    for (int r = 0; r < 16; r++) dis[r] = __builtin_fmaf(-2.0f, acc[r], xn + cnv[r >> 2][r & 3]);
+    for (int r = 0; r < 16; r++) dis[r] = dist_unclamped(acc, r, xn, cnv);
     float m = __builtin_fminf(dis[0], dis[1]);
 #pragma unroll
     for (int r = 2; r < 16; r += 2) m = __builtin_fminf(__builtin_fminf(m, dis[r]), dis[r + 1]);
@@ -143,6 +161,180 @@ __device__ __forceinline__ void epilogue16_spec(float& bestd, unsigned& bestc, c
         bestc = br != 16u ? (codebase | br) : bestc;
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// The steps that the MFMA sweeps below share, once each.  j = lane & 31 is the lane's x row (the accumulator column),
+// h = lane >> 5 the k of each MFMA k-pair that the lane feeds.  A sweep differs from its siblings in what it stages,
+// when it prefetches and when it finishes an accumulator: that schedule is the kernel's body, the arithmetic is here.
+
+// Row xrow of D features as the B operand of half-wave h (xv[i] = feature 2 i + h); returns |x|^2, the ascending fmaf
+// chain.  (The hinted sweep has |x|^2 from the three chains of its guess and drops this one.)
+template <int D>
+__device__ __forceinline__ float load_x_row(const float* xrow, int h, float (&xv)[D / 2]) {
+    const f32x4* p = reinterpret_cast<const f32x4*>(xrow);
+    float nrm = 0.0f;
+#pragma unroll
+    for (int q = 0; q < D / 8; q++) {
+        const f32x4 u = p[2 * q], v = p[2 * q + 1];
+#pragma unroll
+        for (int e = 0; e < 4; e++) nrm = __builtin_fmaf(u[e], u[e], nrm);
+#pragma unroll
+        for (int e = 0; e < 4; e++) nrm = __builtin_fmaf(v[e], v[e], nrm);
+        xv[4 * q + 0] = h ? u[1] : u[0];
+        xv[4 * q + 1] = h ? u[3] : u[2];
+        xv[4 * q + 2] = h ? v[1] : v[0];
+        xv[4 * q + 3] = h ? v[3] : v[2];
+    }
+    return nrm;
+}
+
+// The A fragments of the lane's centroid row, fragment q = features 8 q + {0, 2, 4, 6} + h: read from the swizzled row
+// (in LDS; pruned_reg reads the image itself), or already in registers (pruned_reg loads them a group ahead).
+struct SwizzledRow {
+    const float* row;
+    int j, h;
+    __device__ __forceinline__ f32x4 operator()(int q) const {
+        return *reinterpret_cast<const f32x4*>(row + cs::chunk_slot(j, q, h) * 4);
+    }
+};
+template <int NQ>
+struct RegRow {
+    const f32x4 (&av)[NQ];
+    __device__ __forceinline__ f32x4 operator()(int q) const { return av[q]; }
+};
+
+// acc += fragment q of 32 centroid rows x features 8 q .. 8 q + 7 of 32 x rows: four MFMAs, k ascending in the feature
+// index.  (The loop over q stays in the kernels: unrolled in here, ahead of the kernel's own loops, the compiler lifts the
+// LDS reads out of the row-block loop and hinted<64, 2, 4> grows from 162 to 198 registers.)
+template <typename A, int NX>
+__device__ __forceinline__ void mfma_fragment(f32x16& acc, const A& afrag, int q, const float (&xv)[NX]) {
+    const f32x4 av = afrag(q);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], xv[4 * q + 0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], xv[4 * q + 1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], xv[4 * q + 2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], xv[4 * q + 3], acc, 0, 0, 0);
+}
+
+// |c|^2 of the lane's 16 accumulator rows, 8 g + 4 h + (0..3); cnh: the norm of the half-wave's first row (+ 4 h)
+__device__ __forceinline__ void load_norms16(const float* cnh, f32x4 (&cnv)[4]) {
+#pragma unroll
+    for (int g = 0; g < 4; g++) cnv[g] = *reinterpret_cast<const f32x4*>(cnh + 8 * g);
+}
+
+// A finished accumulator of a sweep that starts from a guess (hinted, pruned).  The minimum of the 16 unclamped
+// distances costs 2.5 VALU per element instead of 6 (nothing kept: the rare exact update recomputes them from the
+// accumulator); a clamped distance can tie or beat the running best (>= 0) only if the unclamped one does.
+__device__ __forceinline__ float min16_unclamped(const f32x16& acc, float xn, const f32x4 (&cnv)[4]) {
+    float m = __builtin_inff();
+#pragma unroll
+    for (int r = 0; r < 16; r += 2)
+        m = __builtin_fminf(__builtin_fminf(m, dist_unclamped(acc, r, xn, cnv)), dist_unclamped(acc, r + 1, xn, cnv));
+    return m;
+}
+
+// The order of the exact update: lexicographic in (distance, index), so that the answer is the brute-force arg-min with
+// lowest-index ties whatever the guess was.  (By value: on references the && stays a branch per register.)
+__device__ __forceinline__ bool lex_better(float dd, unsigned idx, float bd, unsigned bi) {
+    return dd < bd || (dd == bd && idx < bi);
+}
+
+// The pruned sweeps' update: entered only when some lane of the wave needs it; tab: the index table in the group's pad
+// (+ 4 h), which maps the half-wave's image rows back to centroids.
+__device__ __forceinline__ void lex_update16(float& bestd, unsigned& besti, const f32x16& acc, float xn,
+                                             const f32x4 (&cnv)[4], const unsigned* tab) {
+    if (__builtin_amdgcn_ballot_w64(min16_unclamped(acc, xn, cnv) <= bestd) != 0) {
+        float bd = bestd;
+        unsigned bi = besti;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const float dd = __builtin_fmaxf(dist_unclamped(acc, r, xn, cnv), 0.0f);
+            const unsigned idx = tab[cs::reg_offset(r)];
+            const bool better = lex_better(dd, idx, bd, bi);
+            bd = better ? dd : bd;
+            bi = better ? idx : bi;
+        }
+        bestd = bd;
+        besti = bi;
+    }
+}
+
+// The answer of one row: the two half-waves (same rows, disjoint centroids) merged and, by the lanes with `mine` (half-wave
+// 0, row < n), stored at `row`.  fi is a centroid index: the dense sweeps come with cs::index_of(code, h).
+__device__ __forceinline__ void store_answer(float fd, unsigned fi, long row, bool mine, long* ids, float* dist) {
+    cs::merge_halves_min(fd, fi);
+    if (mine) {
+        ids[row] = no_winner(fi, fd) ? -1L : (long)fi;
+        if (dist) dist[row] = fd;
+    }
+}
+
+// What a wave of the pruned sweeps holds for its 32 NB rows (positions pos0 .. of the visiting order): the rows as
+// the B operand, the running best from the pre-pass's exact distance to the guess, and the rows' mask words over the
+// 32-centroid groups in scalar registers (ng <= 512).
+template <int D, int NB>
+struct PrunedRows {
+    static constexpr int MAXW = 16;  // mask words kept in scalar registers
+    float xr[NB][D / 2];
+    float xn[NB];
+    float bestd[NB];
+    unsigned besti[NB];
+    long rowid[NB];
+    uint32_t mw[NB][MAXW];
+    uint32_t any[MAXW];
+    int ng, ngw;
+
+    __device__ __forceinline__ PrunedRows(const float* X, long n, const uint32_t* order,
+                                          const uint32_t* hint_sorted, const float* bd_in,
+                                          const uint32_t* mask, int ng_, int ngw_, long pos0, int j, int h)
+        : ng(ng_), ngw(ngw_) {
+        const long ntile32 = (n + 31) / 32;
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            long pos = pos0 + 32 * b + j;
+            if (pos >= n) pos = n - 1;
+            const long r = (long)order[pos];
+            rowid[b] = r;
+            xn[b] = load_x_row<D>(X + r * D, h, xr[b]);
+            bestd[b] = bd_in[pos];
+            besti[b] = bestd[b] < __builtin_inff() ? hint_sorted[pos] : 0xffffffffu;
+            const long tile = pos0 / 32 + b;
+#pragma unroll
+            for (int w = 0; w < MAXW; w++) {
+                uint32_t m = 0;
+                if (w < ngw && tile < ntile32) m = mask[(size_t)tile * ngw + w];
+                mw[b][w] = __builtin_amdgcn_readfirstlane(m);
+            }
+        }
+#pragma unroll
+        for (int w = 0; w < MAXW; w++) {
+            any[w] = 0;
+#pragma unroll
+            for (int b = 0; b < NB; b++) any[w] |= mw[b][w];
+        }
+    }
+
+    static __device__ __forceinline__ uint32_t word_of(const uint32_t (&m)[MAXW], int w) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int i = 0; i < MAXW; i++)
+            if (i == w) v = m[i];
+        return v;
+    }
+    // first group >= from that some row tile of the wave needs, or ng
+    __device__ __forceinline__ int next_group(int from) const {
+        int w = from >> 5;
+        if (w >= ngw) return ng;
+        uint32_t bits = word_of(any, w) & (0xffffffffu << (from & 31));
+        while (bits == 0) {
+            if (++w >= ngw) return ng;
+            bits = word_of(any, w);
+        }
+        const int g = (w << 5) + __builtin_ctz(bits);
+        return g < ng ? g : ng;
+    }
+    // does row tile b need group g (wave-uniform)
+    __device__ __forceinline__ bool needs(int b, int g) const { return (word_of(mw[b], g >> 5) & (1u << (g & 31))) != 0u; }
+};
 
 // ---------------------------------------------------------------------------------------------
 template <int D, int NB, int NA, bool DMA, int WAVES_PER_SIMD, bool SPEC = false>
@@ -170,25 +362,7 @@ assign_mfma_kernel(const float* __restrict__ X, long n, const float* __restrict_
     for (int b = 0; b < NB; b++) {
         long r = row0 + 32 * b + j;
         if (r >= n) r = n - 1;
-        const f32x4* p = reinterpret_cast<const f32x4*>(X + r * D);
-        float nrm = 0.0f;
-#pragma unroll
-        for (int q = 0; q < D / 8; q++) {
-            const f32x4 u = p[2 * q], v = p[2 * q + 1];
-            nrm = __builtin_fmaf(u[0], u[0], nrm);
-            nrm = __builtin_fmaf(u[1], u[1], nrm);
-            nrm = __builtin_fmaf(u[2], u[2], nrm);
-            nrm = __builtin_fmaf(u[3], u[3], nrm);
-            nrm = __builtin_fmaf(v[0], v[0], nrm);
-            nrm = __builtin_fmaf(v[1], v[1], nrm);
-            nrm = __builtin_fmaf(v[2], v[2], nrm);
-            nrm = __builtin_fmaf(v[3], v[3], nrm);
-            xr[b][4 * q + 0] = h ? u[1] : u[0];
-            xr[b][4 * q + 1] = h ? u[3] : u[2];
-            xr[b][4 * q + 2] = h ? v[1] : v[0];
-            xr[b][4 * q + 3] = h ? v[3] : v[2];
-        }
-        xn[b] = nrm;
+        xn[b] = load_x_row<D>(X + r * D, h, xr[b]);
     }
 
     float bestd[NB];
@@ -200,7 +374,9 @@ assign_mfma_kernel(const float* __restrict__ X, long n, const float* __restrict_
     }
 
     // ---- stage tile 0 ----
-    auto stage_dma = [&](int tile, float* dst) {
+    // (the staging stays a lambda in this kernel and in the hinted one: as a shared function it cost both 0.5 to 0.9 %
+    // at d = 64, profiles/assign_steps_time.jsonl; the pruned and the any-d sweep stage other units anyway)
+    auto stage_tile = [&](int tile, float* dst) {
         const float* src = img + (size_t)tile * TILE_F;
 #pragma unroll
         for (int p0 = 0; p0 < PIECES; p0 += 4) {
@@ -210,7 +386,7 @@ assign_mfma_kernel(const float* __restrict__ X, long n, const float* __restrict_
     };
     f32x4 pf[DMA ? 1 : VPT];
     if constexpr (DMA) {
-        stage_dma(0, smem);
+        stage_tile(0, smem);
     } else {
         const f32x4* src = reinterpret_cast<const f32x4*>(img);
 #pragma unroll
@@ -228,13 +404,12 @@ assign_mfma_kernel(const float* __restrict__ X, long n, const float* __restrict_
     for (int g = 0; g < 4; g++) cnP[g] = {__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff()};
     unsigned codeP = 0u;
 
-    const int swz = j & 15;
     for (int ct = 0; ct < ntiles; ct++) {
         const float* cur = smem + (ct & 1) * TILE_F;
         const bool more = ct + 1 < ntiles;
         if (more) {
             if constexpr (DMA) {
-                stage_dma(ct + 1, smem + ((ct + 1) & 1) * TILE_F);
+                stage_tile(ct + 1, smem + ((ct + 1) & 1) * TILE_F);
             } else {
                 const f32x4* src = reinterpret_cast<const f32x4*>(img + (size_t)(ct + 1) * TILE_F);
 #pragma unroll
@@ -247,25 +422,15 @@ assign_mfma_kernel(const float* __restrict__ X, long n, const float* __restrict_
 
 #pragma unroll
         for (int a = 0; a < NA; a++) {
-            // |c|^2 of this lane's 16 accumulator rows: rows a*32 + 8g + 4h + (0..3)
             f32x4 cnv[4];
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-                cnv[g] = *reinterpret_cast<const f32x4*>(cur + R * D + a * 32 + 8 * g + 4 * h);
-            const float* arow = cur + (a * 32 + j) * D;
+            load_norms16(cur + R * D + a * 32 + 4 * h, cnv);
+            const SwizzledRow arow{cur + (a * 32 + j) * D, j, h};
             const unsigned codebase = (unsigned)(ct * NA + a) * 16u;
 #pragma unroll
             for (int b = 0; b < NB; b++) {
                 f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-                for (int q = 0; q < D / 8; q++) {
-                    const int pc = (2 * q + h) ^ swz;
-                    const f32x4 av = *reinterpret_cast<const f32x4*>(arow + pc * 4);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], xr[b][4 * q + 0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], xr[b][4 * q + 1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], xr[b][4 * q + 2], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], xr[b][4 * q + 3], acc, 0, 0, 0);
-                }
+                for (int q = 0; q < D / 8; q++) mfma_fragment(acc, arow, q, xr[b]);
                 if constexpr (SPEC) {
                     epilogue16_spec(bestd[b], bestc[b], acc, xn[b], cnv, codebase);
                     continue;
@@ -297,27 +462,10 @@ assign_mfma_kernel(const float* __restrict__ X, long n, const float* __restrict_
     }
     epilogue16(bestd[NB - 1], bestc[NB - 1], accP, xn[NB - 1], cnP, codeP);
 
-    // ---- merge the two half-waves (rows 4h + ... of every 8-row group) and store ----
 #pragma unroll
     for (int b = 0; b < NB; b++) {
-        int idx = -1;
-        if (bestc[b] != 0xffffffffu) {
-            const unsigned r = bestc[b] & 15u;
-            idx = (int)((bestc[b] >> 4) * 32u + (r & 3u) + 8u * (r >> 2) + 4u * (unsigned)h);
-        }
-        const float od = __shfl_xor(bestd[b], 32);
-        const int oi = __shfl_xor(idx, 32);
-        float fd = bestd[b];
-        int fi = idx;
-        if (od < fd || (od == fd && (unsigned)oi < (unsigned)fi)) {
-            fd = od;
-            fi = oi;
-        }
         const long r = row0 + 32 * b + j;
-        if (h == 0 && r < n) {
-            ids[r] = (long)fi;
-            if (dist) dist[r] = fd;
-        }
+        store_answer(bestd[b], cs::index_of(bestc[b], h), r, h == 0 && r < n, ids, dist);
     }
 }
 
@@ -378,21 +526,14 @@ assign_mfma_hinted_kernel(const float* __restrict__ X, long n, const float* __re
                 ip = __builtin_fmaf(cu[e], u[e], ip);
             }
         }
-#pragma unroll
-        for (int q = 0; q < D / 8; q++) {
-            const f32x4 u = p[2 * q], v = p[2 * q + 1];
-            xr[b][4 * q + 0] = h ? u[1] : u[0];
-            xr[b][4 * q + 1] = h ? u[3] : u[2];
-            xr[b][4 * q + 2] = h ? v[1] : v[0];
-            xr[b][4 * q + 3] = h ? v[3] : v[2];
-        }
+        load_x_row<D>(X + r * D, h, xr[b]);
         xn[b] = nrm;
         const float dh = __builtin_fmaxf(__builtin_fmaf(-2.0f, ip, nrm + cnn), 0.0f);
         bestd[b] = has ? dh : __builtin_inff();
         besti[b] = has ? (unsigned)g : 0xffffffffu;
     }
 
-    auto stage_dma = [&](int tile, float* dst) {
+    auto stage_tile = [&](int tile, float* dst) {
         const float* src = img + (size_t)tile * TILE_F;
 #pragma unroll
         for (int p0 = 0; p0 < PIECES; p0 += 4) {
@@ -400,52 +541,33 @@ assign_mfma_hinted_kernel(const float* __restrict__ X, long n, const float* __re
             if (p < PIECES) dma_1k(src + p * 256 + lane * 4, dst + p * 256);
         }
     };
-    stage_dma(0, smem);
+    stage_tile(0, smem);
     __syncthreads();
 
-    const int swz = j & 15;
     for (int ct = 0; ct < ntiles; ct++) {
         const float* cur = smem + (ct & 1) * TILE_F;
-        if (ct + 1 < ntiles) stage_dma(ct + 1, smem + ((ct + 1) & 1) * TILE_F);
+        if (ct + 1 < ntiles) stage_tile(ct + 1, smem + ((ct + 1) & 1) * TILE_F);
 #pragma unroll
         for (int a = 0; a < NA; a++) {
             f32x4 cnv[4];
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-                cnv[g] = *reinterpret_cast<const f32x4*>(cur + R * D + a * 32 + 8 * g + 4 * h);
-            const float* arow = cur + (a * 32 + j) * D;
-            const unsigned jobbase = (unsigned)(ct * NA + a) * 32u + 4u * (unsigned)h;
+            load_norms16(cur + R * D + a * 32 + 4 * h, cnv);
+            const SwizzledRow arow{cur + (a * 32 + j) * D, j, h};
+            const unsigned jobbase = (unsigned)cs::acc_base(ct * NA + a, h);
 #pragma unroll
             for (int b = 0; b < NB; b++) {
                 f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-                for (int q = 0; q < D / 8; q++) {
-                    const int pcx = (2 * q + h) ^ swz;
-                    const f32x4 av = *reinterpret_cast<const f32x4*>(arow + pcx * 4);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], xr[b][4 * q + 0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], xr[b][4 * q + 1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], xr[b][4 * q + 2], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], xr[b][4 * q + 3], acc, 0, 0, 0);
-                }
-                // minimum of the 16 unclamped distances (nothing kept: the rare exact update below
-                // recomputes them from the accumulator)
-                float m = __builtin_inff();
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const float d0 = __builtin_fmaf(-2.0f, acc[r], xn[b] + cnv[r >> 2][r & 3]);
-                    const float d1 = __builtin_fmaf(-2.0f, acc[r + 1], xn[b] + cnv[(r + 1) >> 2][(r + 1) & 3]);
-                    m = __builtin_fminf(__builtin_fminf(m, d0), d1);
-                }
-                // a clamped distance can tie or beat bestd (>= 0) only if the unclamped one does
-                if (__builtin_amdgcn_ballot_w64(m <= bestd[b]) != 0) {
+                for (int q = 0; q < D / 8; q++) mfma_fragment(acc, arow, q, xr[b]);
+                // (written out, not lex_update16 with an index functor: in a helper the sixteen indices, the same for
+                // every b, are lifted out of the row-block loop and <64, 2, 4> grows from 162 to 183 registers)
+                if (__builtin_amdgcn_ballot_w64(min16_unclamped(acc, xn[b], cnv) <= bestd[b]) != 0) {
                     float bd = bestd[b];
                     unsigned bi = besti[b];
 #pragma unroll
                     for (int r = 0; r < 16; r++) {
-                        const float dd = __builtin_fmaxf(
-                            __builtin_fmaf(-2.0f, acc[r], xn[b] + cnv[r >> 2][r & 3]), 0.0f);
-                        const unsigned idx = jobbase + (unsigned)((r & 3) + 8 * (r >> 2));
-                        const bool better = dd < bd || (dd == bd && idx < bi);
+                        const float dd = __builtin_fmaxf(dist_unclamped(acc, r, xn[b], cnv), 0.0f);
+                        const unsigned idx = jobbase + (unsigned)cs::reg_offset(r);
+                        const bool better = lex_better(dd, idx, bd, bi);
                         bd = better ? dd : bd;
                         bi = better ? idx : bi;
                     }
@@ -458,21 +580,7 @@ assign_mfma_hinted_kernel(const float* __restrict__ X, long n, const float* __re
     }
 
 #pragma unroll
-    for (int b = 0; b < NB; b++) {
-        const float od = __shfl_xor(bestd[b], 32);
-        const unsigned oi = (unsigned)__shfl_xor((int)besti[b], 32);
-        float fd = bestd[b];
-        unsigned fi = besti[b];
-        if (od < fd || (od == fd && oi < fi)) {
-            fd = od;
-            fi = oi;
-        }
-        const long pos = pos0 + 32 * b + j;
-        if (h == 0 && pos < n) {
-            ids[rowid[b]] = no_winner(fi, fd) ? -1L : (long)fi;
-            if (dist) dist[rowid[b]] = fd;
-        }
-    }
+    for (int b = 0; b < NB; b++) store_answer(bestd[b], besti[b], rowid[b], h == 0 && pos0 + 32 * b + j < n, ids, dist);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -491,30 +599,15 @@ __global__ void __launch_bounds__(WG) prep_centroids_perm_kernel(const float* __
     const int chunks_per_row = d / 4;
     for (int e = threadIdx.x; e < R * chunks_per_row; e += WG) {
         const int r = e / chunks_per_row, pc = e % chunks_per_row;
-        const int lc = pc ^ (r & 15);
-        const int q = lc >> 1, h = lc & 1;
         const int slot = t * R + r;
         const int row = slot < kp ? cperm[slot] : -1;
-        f32x4 v;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int f = 8 * q + 2 * u + h;
-            v[u] = (row >= 0 && f < d) ? c[(size_t)row * d + f] : 0.0f;
-        }
-        *reinterpret_cast<f32x4*>(out + (size_t)r * d + pc * 4) = v;
+        *reinterpret_cast<f32x4*>(out + (size_t)r * d + pc * 4) =
+            image_slot(row >= 0 ? c + (size_t)row * d : nullptr, d, 0, r, pc);
     }
     for (int r = threadIdx.x; r < 128; r += WG) {
         const int slot = t * R + r;
         const int row = (r < R && slot < kp) ? cperm[slot] : -1;
-        float nrm = __builtin_inff();
-        if (row >= 0) {
-            nrm = 0.0f;
-            for (int f = 0; f < d; f++) {
-                const float v = c[(size_t)row * d + f];
-                nrm = __builtin_fmaf(v, v, nrm);
-            }
-        }
-        out[R * d + r] = nrm;
+        out[R * d + r] = image_norm(row >= 0 ? c + (size_t)row * d : nullptr, d);
         reinterpret_cast<unsigned*>(out)[R * d + 128 + r] = row >= 0 ? (unsigned)row : 0xffffffffu;
     }
 }
@@ -533,156 +626,50 @@ assign_mfma_pruned_kernel(const float* __restrict__ X, long n, const float* __re
                           long* __restrict__ ids, float* __restrict__ dist) {
     constexpr int GROUP_F = 32 * D + GROUP_PAD;
     constexpr int PIECES = GROUP_F / 256;
-    constexpr int MAXW = 16;  // mask words kept in scalar registers (ng <= 512)
     extern __shared__ __attribute__((aligned(16))) float smem[];  // 2 * GROUP_F floats
 
     const int lane = threadIdx.x;
     const int j = lane & 31;
     const int h = lane >> 5;
     const long pos0 = (long)blockIdx.x * (32 * NB);
-    const long ntile32 = (n + 31) / 32;
 
-    float xr[NB][D / 2];
-    float xn[NB];
-    float bestd[NB];
-    unsigned besti[NB];
-    long rowid[NB];
-    uint32_t mw[NB][MAXW];
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-        long pos = pos0 + 32 * b + j;
-        if (pos >= n) pos = n - 1;
-        const long r = (long)order[pos];
-        rowid[b] = r;
-        const f32x4* p = reinterpret_cast<const f32x4*>(X + r * D);
-        float nrm = 0.0f;
-#pragma unroll
-        for (int q = 0; q < D / 8; q++) {
-            const f32x4 u = p[2 * q], v = p[2 * q + 1];
-#pragma unroll
-            for (int e = 0; e < 4; e++) nrm = __builtin_fmaf(u[e], u[e], nrm);
-#pragma unroll
-            for (int e = 0; e < 4; e++) nrm = __builtin_fmaf(v[e], v[e], nrm);
-            xr[b][4 * q + 0] = h ? u[1] : u[0];
-            xr[b][4 * q + 1] = h ? u[3] : u[2];
-            xr[b][4 * q + 2] = h ? v[1] : v[0];
-            xr[b][4 * q + 3] = h ? v[3] : v[2];
-        }
-        xn[b] = nrm;
-        bestd[b] = bd_in[pos];
-        besti[b] = bestd[b] < __builtin_inff() ? hint_sorted[pos] : 0xffffffffu;
-        const long tile = pos0 / 32 + b;
-#pragma unroll
-        for (int w = 0; w < MAXW; w++) {
-            uint32_t m = 0;
-            if (w < ngw && tile < ntile32) m = mask[(size_t)tile * ngw + w];
-            mw[b][w] = __builtin_amdgcn_readfirstlane(m);
-        }
-    }
-    uint32_t any[MAXW];
-#pragma unroll
-    for (int w = 0; w < MAXW; w++) {
-        any[w] = 0;
-#pragma unroll
-        for (int b = 0; b < NB; b++) any[w] |= mw[b][w];
-    }
-    auto word_of = [&](const uint32_t (&m)[MAXW], int w) -> uint32_t {
-        uint32_t v = 0;
-#pragma unroll
-        for (int i = 0; i < MAXW; i++)
-            if (i == w) v = m[i];
-        return v;
-    };
-    auto next_group = [&](int from) {  // first needed group >= from, or ng
-        int w = from >> 5;
-        if (w >= ngw) return ng;
-        uint32_t bits = word_of(any, w) & (0xffffffffu << (from & 31));
-        while (bits == 0) {
-            if (++w >= ngw) return ng;
-            bits = word_of(any, w);
-        }
-        const int g = (w << 5) + __builtin_ctz(bits);
-        return g < ng ? g : ng;
-    };
-    auto stage_dma = [&](int g, float* dst) {
+    PrunedRows<D, NB> rows(X, n, order, hint_sorted, bd_in, mask, ng, ngw, pos0, j, h);
+    auto stage_group = [&](int g, float* dst) {
         const float* src = img + (size_t)g * GROUP_F;
 #pragma unroll
         for (int p = 0; p < PIECES; p++) dma_1k(src + p * 256 + lane * 4, dst + p * 256);
     };
 
-    int g = next_group(0);
+    int g = rows.next_group(0);
     int buf = 0;
-    if (g < ng) stage_dma(g, smem);
-    const int swz = j & 15;
+    if (g < ng) stage_group(g, smem);
     while (g < ng) {
         const float* cur = smem + buf * GROUP_F;
         // the group being consumed has landed once every DMA this wave issued so far is done; the
         // reads of the other buffer (previous group) were all consumed by that group's MFMAs
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int nxt = next_group(g + 1);
-        if (nxt < ng) stage_dma(nxt, smem + (buf ^ 1) * GROUP_F);
+        const int nxt = rows.next_group(g + 1);
+        if (nxt < ng) stage_group(nxt, smem + (buf ^ 1) * GROUP_F);
 
         f32x4 cnv[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) cnv[q] = *reinterpret_cast<const f32x4*>(cur + 32 * D + 8 * q + 4 * h);
-        const float* arow = cur + j * D;
+        load_norms16(cur + 32 * D + 4 * h, cnv);
+        const SwizzledRow arow{cur + j * D, j, h};
         const unsigned* idxrow = reinterpret_cast<const unsigned*>(cur) + 32 * D + 128 + 4 * h;
-        const uint32_t gbit = 1u << (g & 31);
 #pragma unroll
         for (int b = 0; b < NB; b++) {
-            if ((word_of(mw[b], g >> 5) & gbit) == 0u) continue;  // wave-uniform
+            if (!rows.needs(b, g)) continue;
             f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-            for (int q = 0; q < D / 8; q++) {
-                const int pcx = (2 * q + h) ^ swz;
-                const f32x4 av = *reinterpret_cast<const f32x4*>(arow + pcx * 4);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], xr[b][4 * q + 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], xr[b][4 * q + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], xr[b][4 * q + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], xr[b][4 * q + 3], acc, 0, 0, 0);
-            }
-            float m = __builtin_inff();
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const float d0 = __builtin_fmaf(-2.0f, acc[r], xn[b] + cnv[r >> 2][r & 3]);
-                const float d1 = __builtin_fmaf(-2.0f, acc[r + 1], xn[b] + cnv[(r + 1) >> 2][(r + 1) & 3]);
-                m = __builtin_fminf(__builtin_fminf(m, d0), d1);
-            }
-            if (__builtin_amdgcn_ballot_w64(m <= bestd[b]) != 0) {
-                float bd = bestd[b];
-                unsigned bi = besti[b];
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const float dd = __builtin_fmaxf(__builtin_fmaf(-2.0f, acc[r], xn[b] + cnv[r >> 2][r & 3]), 0.0f);
-                    const unsigned idx = idxrow[(r & 3) + 8 * (r >> 2)];
-                    const bool better = dd < bd || (dd == bd && idx < bi);
-                    bd = better ? dd : bd;
-                    bi = better ? idx : bi;
-                }
-                bestd[b] = bd;
-                besti[b] = bi;
-            }
+            for (int q = 0; q < D / 8; q++) mfma_fragment(acc, arow, q, rows.xr[b]);
+            lex_update16(rows.bestd[b], rows.besti[b], acc, rows.xn[b], cnv, idxrow);
         }
         g = nxt;
         buf ^= 1;
     }
 
 #pragma unroll
-    for (int b = 0; b < NB; b++) {
-        const float od = __shfl_xor(bestd[b], 32);
-        const unsigned oi = (unsigned)__shfl_xor((int)besti[b], 32);
-        float fd = bestd[b];
-        unsigned fi = besti[b];
-        if (od < fd || (od == fd && oi < fi)) {
-            fd = od;
-            fi = oi;
-        }
-        const long pos = pos0 + 32 * b + j;
-        if (h == 0 && pos < n) {
-            ids[rowid[b]] = no_winner(fi, fd) ? -1L : (long)fi;
-            if (dist) dist[rowid[b]] = fd;
-        }
-    }
+    for (int b = 0; b < NB; b++)
+        store_answer(rows.bestd[b], rows.besti[b], rows.rowid[b], h == 0 && pos0 + 32 * b + j < n, ids, dist);
 }
 
 // Register-staged form of the pruned sweep: the A fragments of the NEXT needed group are loaded
@@ -697,155 +684,50 @@ assign_mfma_pruned_reg_kernel(const float* __restrict__ X, long n, const float* 
                               long* __restrict__ ids, float* __restrict__ dist) {
     constexpr int GROUP_F = 32 * D + GROUP_PAD;
     constexpr int NQ = D / 8;
-    constexpr int MAXW = 16;
 
     const int lane = threadIdx.x;
     const int j = lane & 31;
     const int h = lane >> 5;
     const long pos0 = (long)blockIdx.x * (32 * NB);
-    const long ntile32 = (n + 31) / 32;
 
-    float xr[NB][D / 2];
-    float xn[NB];
-    float bestd[NB];
-    unsigned besti[NB];
-    long rowid[NB];
-    uint32_t mw[NB][MAXW];
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-        long pos = pos0 + 32 * b + j;
-        if (pos >= n) pos = n - 1;
-        const long r = (long)order[pos];
-        rowid[b] = r;
-        const f32x4* p = reinterpret_cast<const f32x4*>(X + r * D);
-        float nrm = 0.0f;
-#pragma unroll
-        for (int q = 0; q < D / 8; q++) {
-            const f32x4 u = p[2 * q], v = p[2 * q + 1];
-#pragma unroll
-            for (int e = 0; e < 4; e++) nrm = __builtin_fmaf(u[e], u[e], nrm);
-#pragma unroll
-            for (int e = 0; e < 4; e++) nrm = __builtin_fmaf(v[e], v[e], nrm);
-            xr[b][4 * q + 0] = h ? u[1] : u[0];
-            xr[b][4 * q + 1] = h ? u[3] : u[2];
-            xr[b][4 * q + 2] = h ? v[1] : v[0];
-            xr[b][4 * q + 3] = h ? v[3] : v[2];
-        }
-        xn[b] = nrm;
-        bestd[b] = bd_in[pos];
-        besti[b] = bestd[b] < __builtin_inff() ? hint_sorted[pos] : 0xffffffffu;
-        const long tile = pos0 / 32 + b;
-#pragma unroll
-        for (int w = 0; w < MAXW; w++) {
-            uint32_t m = 0;
-            if (w < ngw && tile < ntile32) m = mask[(size_t)tile * ngw + w];
-            mw[b][w] = __builtin_amdgcn_readfirstlane(m);
-        }
-    }
-    uint32_t any[MAXW];
-#pragma unroll
-    for (int w = 0; w < MAXW; w++) {
-        any[w] = 0;
-#pragma unroll
-        for (int b = 0; b < NB; b++) any[w] |= mw[b][w];
-    }
-    auto word_of = [&](const uint32_t (&m)[MAXW], int w) -> uint32_t {
-        uint32_t v = 0;
-#pragma unroll
-        for (int i = 0; i < MAXW; i++)
-            if (i == w) v = m[i];
-        return v;
-    };
-    auto next_group = [&](int from) {
-        int w = from >> 5;
-        if (w >= ngw) return ng;
-        uint32_t bits = word_of(any, w) & (0xffffffffu << (from & 31));
-        while (bits == 0) {
-            if (++w >= ngw) return ng;
-            bits = word_of(any, w);
-        }
-        const int g = (w << 5) + __builtin_ctz(bits);
-        return g < ng ? g : ng;
-    };
+    PrunedRows<D, NB> rows(X, n, order, hint_sorted, bd_in, mask, ng, ngw, pos0, j, h);
 
-    const int swz = j & 15;
     auto load_group = [&](int g, f32x4 (&av)[NQ], f32x4 (&cn)[4]) {
         const float* base = img + (size_t)g * GROUP_F;
-        const float* arow = base + j * D;
+        const SwizzledRow arow{base + j * D, j, h};
 #pragma unroll
-        for (int q = 0; q < NQ; q++) av[q] = *reinterpret_cast<const f32x4*>(arow + (((2 * q + h) ^ swz) << 2));
-#pragma unroll
-        for (int q = 0; q < 4; q++) cn[q] = *reinterpret_cast<const f32x4*>(base + 32 * D + 8 * q + 4 * h);
+        for (int q = 0; q < NQ; q++) av[q] = arow(q);
+        load_norms16(base + 32 * D + 4 * h, cn);
     };
     auto compute_group = [&](int g, const f32x4 (&av)[NQ], const f32x4 (&cnv)[4]) {
-        const uint32_t gbit = 1u << (g & 31);
+        const unsigned* idxrow = reinterpret_cast<const unsigned*>(img + (size_t)g * GROUP_F) + 32 * D + 128 + 4 * h;
 #pragma unroll
         for (int b = 0; b < NB; b++) {
-            if ((word_of(mw[b], g >> 5) & gbit) == 0u) continue;  // wave-uniform
+            if (!rows.needs(b, g)) continue;
             f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-            for (int q = 0; q < NQ; q++) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q][0], xr[b][4 * q + 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q][1], xr[b][4 * q + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q][2], xr[b][4 * q + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q][3], xr[b][4 * q + 3], acc, 0, 0, 0);
-            }
-            float m = __builtin_inff();
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const float d0 = __builtin_fmaf(-2.0f, acc[r], xn[b] + cnv[r >> 2][r & 3]);
-                const float d1 = __builtin_fmaf(-2.0f, acc[r + 1], xn[b] + cnv[(r + 1) >> 2][(r + 1) & 3]);
-                m = __builtin_fminf(__builtin_fminf(m, d0), d1);
-            }
-            if (__builtin_amdgcn_ballot_w64(m <= bestd[b]) != 0) {
-                const unsigned* idxrow =
-                    reinterpret_cast<const unsigned*>(img + (size_t)g * GROUP_F) + 32 * D + 128 + 4 * h;
-                float bd = bestd[b];
-                unsigned bi = besti[b];
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const float dd = __builtin_fmaxf(__builtin_fmaf(-2.0f, acc[r], xn[b] + cnv[r >> 2][r & 3]), 0.0f);
-                    const unsigned idx = idxrow[(r & 3) + 8 * (r >> 2)];
-                    const bool better = dd < bd || (dd == bd && idx < bi);
-                    bd = better ? dd : bd;
-                    bi = better ? idx : bi;
-                }
-                bestd[b] = bd;
-                besti[b] = bi;
-            }
+            for (int q = 0; q < NQ; q++) mfma_fragment(acc, RegRow<NQ>{av}, q, rows.xr[b]);
+            lex_update16(rows.bestd[b], rows.besti[b], acc, rows.xn[b], cnv, idxrow);
         }
     };
 
     f32x4 avA[NQ], cnA[4], avB[NQ], cnB[4];
-    int g = next_group(0);
+    int g = rows.next_group(0);
     if (g < ng) load_group(g, avA, cnA);
     while (g < ng) {
-        const int g1 = next_group(g + 1);
+        const int g1 = rows.next_group(g + 1);
         if (g1 < ng) load_group(g1, avB, cnB);
         compute_group(g, avA, cnA);
         if (g1 >= ng) break;
-        const int g2 = next_group(g1 + 1);
+        const int g2 = rows.next_group(g1 + 1);
         if (g2 < ng) load_group(g2, avA, cnA);
         compute_group(g1, avB, cnB);
         g = g2;
     }
 
 #pragma unroll
-    for (int b = 0; b < NB; b++) {
-        const float od = __shfl_xor(bestd[b], 32);
-        const unsigned oi = (unsigned)__shfl_xor((int)besti[b], 32);
-        float fd = bestd[b];
-        unsigned fi = besti[b];
-        if (od < fd || (od == fd && oi < fi)) {
-            fd = od;
-            fi = oi;
-        }
-        const long pos = pos0 + 32 * b + j;
-        if (h == 0 && pos < n) {
-            ids[rowid[b]] = no_winner(fi, fd) ? -1L : (long)fi;
-            if (dist) dist[rowid[b]] = fd;
-        }
-    }
+    for (int b = 0; b < NB; b++)
+        store_answer(rows.bestd[b], rows.besti[b], rows.rowid[b], h == 0 && pos0 + 32 * b + j < n, ids, dist);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -865,28 +747,13 @@ __global__ void __launch_bounds__(WG) prep_centroids_chunked_kernel(const float*
     for (int e = threadIdx.x; e < nchunks * R * chunks16; e += WG) {
         const int ch = e / (R * chunks16);
         const int r = (e / chunks16) % R, pc = e % chunks16;
-        const int lc = cs::chunk_slot(r, pc >> 1, pc & 1);   // the swizzle is an involution: slot pc holds logical slot lc
-        const int q = lc >> 1, h = lc & 1;
         const int row = t * R + r;
-        f32x4 v;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int f = ch * DC + 8 * q + 2 * u + h;
-            v[u] = (row < k && f < d) ? c[(size_t)row * d + f] : 0.0f;
-        }
-        *reinterpret_cast<f32x4*>(out + ((size_t)ch * R + r) * DC + pc * 4) = v;
+        *reinterpret_cast<f32x4*>(out + ((size_t)ch * R + r) * DC + pc * 4) =
+            image_slot(row < k ? c + (size_t)row * d : nullptr, d, ch * DC, r, pc);
     }
     for (int r = threadIdx.x; r < CN_PAD; r += WG) {
         const int row = t * R + r;
-        float nrm = __builtin_inff();
-        if (r < R && row < k) {
-            nrm = 0.0f;
-            for (int f = 0; f < d; f++) {
-                const float v = c[(size_t)row * d + f];
-                nrm = __builtin_fmaf(v, v, nrm);
-            }
-        }
-        out[(size_t)cs::piece_floats(na) * nchunks + r] = nrm;
+        out[(size_t)cs::piece_floats(na) * nchunks + r] = image_norm(r < R && row < k ? c + (size_t)row * d : nullptr, d);
     }
 }
 
@@ -914,15 +781,7 @@ assign_mfma_anyd_kernel(const float* __restrict__ X, long n, int d, int nchunks,
         long r = row0 + 32 * b + j;
         if (r >= n) r = n - 1;
         xrow[b] = X + r * d;
-        float nrm = 0.0f;
-        for (int f = 0; f < d; f += 4) {
-            const f32x4 u = *reinterpret_cast<const f32x4*>(xrow[b] + f);
-            nrm = __builtin_fmaf(u[0], u[0], nrm);
-            nrm = __builtin_fmaf(u[1], u[1], nrm);
-            nrm = __builtin_fmaf(u[2], u[2], nrm);
-            nrm = __builtin_fmaf(u[3], u[3], nrm);
-        }
-        xn[b] = nrm;
+        xn[b] = cs::sqnorm16(xrow[b], d);
     }
 
     float bestd[NB];
@@ -934,16 +793,15 @@ assign_mfma_anyd_kernel(const float* __restrict__ X, long n, int d, int nchunks,
     }
 
     // piece s = ct * nchunks + ch lives at img + ct*tile_f + ch*PIECE_F; the last chunk drags the
-    // norms along (they sit right behind it)
-    auto stage_dma = [&](int ct, int ch, float* dst) {
+    // norms along (they sit right behind it), so the count of 1 KiB pieces is known only here
+    auto stage_piece = [&](int ct, int ch, float* dst) {
         const float* src = img + (size_t)ct * tile_f + (size_t)ch * PIECE_F;
         const int pieces = (ch == nchunks - 1 ? BUF_F : PIECE_F) / 256;
         for (int p = wave; p < pieces; p += 4) dma_1k(src + p * 256 + lane * 4, dst + p * 256);
     };
-    stage_dma(0, 0, smem);
+    stage_piece(0, 0, smem);
     __syncthreads();
 
-    const int swz = j & 15;
     const int nstages = ntiles * nchunks;
     int ct = 0, ch = 0;
     f32x16 acc[NA][NB];
@@ -953,19 +811,7 @@ assign_mfma_anyd_kernel(const float* __restrict__ X, long n, int d, int nchunks,
     // and waited: 41-55 % of the fp32 MFMA peak at d = 640).
     auto load_x = [&](int chx, float (&xr)[NB][DC / 2]) {
 #pragma unroll
-        for (int b = 0; b < NB; b++) {
-#pragma unroll
-            for (int q = 0; q < DC / 8; q++) {
-                const int f = chx * DC + 8 * q;
-                f32x4 u = {0, 0, 0, 0}, v = {0, 0, 0, 0};
-                if (f < d) u = *reinterpret_cast<const f32x4*>(xrow[b] + f);          // d % 4 == 0
-                if (f + 4 < d) v = *reinterpret_cast<const f32x4*>(xrow[b] + f + 4);
-                xr[b][4 * q + 0] = h ? u[1] : u[0];
-                xr[b][4 * q + 1] = h ? u[3] : u[2];
-                xr[b][4 * q + 2] = h ? v[1] : v[0];
-                xr[b][4 * q + 3] = h ? v[3] : v[2];
-            }
-        }
+        for (int b = 0; b < NB; b++) cs::load_x_chunk(xrow[b], chx, d, h, xr[b]);
     };
     auto stage = [&](int s, const float (&xr)[NB][DC / 2], float (&xr_next)[NB][DC / 2]) {
         const float* cur = smem + (s & 1) * BUF_F;
@@ -973,26 +819,19 @@ assign_mfma_anyd_kernel(const float* __restrict__ X, long n, int d, int nchunks,
             int nct = ct, nch = ch + 1;
             if (nch == nchunks) { nch = 0; nct++; }
             if (s + 1 < nstages) {
-                stage_dma(nct, nch, smem + ((s + 1) & 1) * BUF_F);
+                stage_piece(nct, nch, smem + ((s + 1) & 1) * BUF_F);
                 load_x(nch, xr_next);
             }
         }
 #pragma unroll
         for (int a = 0; a < NA; a++) {
-            const float* arow = cur + (a * 32 + j) * DC;
+            const SwizzledRow arow{cur + (a * 32 + j) * DC, j, h};
 #pragma unroll
             for (int b = 0; b < NB; b++) {
                 f32x16 cacc = acc[a][b];
                 if (ch == 0) cacc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-                for (int q = 0; q < DC / 8; q++) {
-                    const int pc = (2 * q + h) ^ swz;   // cs::chunk_slot(j, q, h)
-                    const f32x4 av = *reinterpret_cast<const f32x4*>(arow + pc * 4);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], xr[b][4 * q + 0], cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], xr[b][4 * q + 1], cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2], xr[b][4 * q + 2], cacc, 0, 0, 0);
-                    cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[3], xr[b][4 * q + 3], cacc, 0, 0, 0);
-                }
+                for (int q = 0; q < DC / 8; q++) mfma_fragment(cacc, arow, q, xr[b]);
                 acc[a][b] = cacc;
             }
         }
@@ -1000,9 +839,7 @@ assign_mfma_anyd_kernel(const float* __restrict__ X, long n, int d, int nchunks,
 #pragma unroll
             for (int a = 0; a < NA; a++) {
                 f32x4 cnv[4];
-#pragma unroll
-                for (int g = 0; g < 4; g++)
-                    cnv[g] = *reinterpret_cast<const f32x4*>(cur + PIECE_F + a * 32 + 8 * g + 4 * h);
+                load_norms16(cur + PIECE_F + a * 32 + 4 * h, cnv);
                 const unsigned codebase = (unsigned)(ct * NA + a) * 16u;
 #pragma unroll
                 for (int b = 0; b < NB; b++) epilogue16(bestd[b], bestc[b], acc[a][b], xn[b], cnv, codebase);
@@ -1020,24 +857,8 @@ assign_mfma_anyd_kernel(const float* __restrict__ X, long n, int d, int nchunks,
 
 #pragma unroll
     for (int b = 0; b < NB; b++) {
-        int idx = -1;
-        if (bestc[b] != 0xffffffffu) {
-            const unsigned r = bestc[b] & 15u;
-            idx = (int)((bestc[b] >> 4) * 32u + (r & 3u) + 8u * (r >> 2) + 4u * (unsigned)h);
-        }
-        const float od = __shfl_xor(bestd[b], 32);
-        const int oi = __shfl_xor(idx, 32);
-        float fd = bestd[b];
-        int fi = idx;
-        if (od < fd || (od == fd && (unsigned)oi < (unsigned)fi)) {
-            fd = od;
-            fi = oi;
-        }
         const long r = row0 + 32 * b + j;
-        if (h == 0 && r < n) {
-            ids[r] = (long)fi;
-            if (dist) dist[r] = fd;
-        }
+        store_answer(bestd[b], cs::index_of(bestc[b], h), r, h == 0 && r < n, ids, dist);
     }
 }
 
@@ -1259,15 +1080,19 @@ static int launch_pruned_sweep(at_ctx* ctx, const at_exact_call& call, int64_t n
                                const uint32_t* hint_sorted) {
     const size_t lds = 2 * sizeof(float) * tile_floats(D, 1);
     const int64_t rows_per_wg = 32 * NB;
-    // d = 64: register-staged A operand (no LDS); AT_PRUNE_KERNEL=0 selects the LDS-DMA form (A/B aid)
-    if (ctx->dbg.prune_kernel != 0 && D == 64 && NB <= 2)
-        AT_LAUNCH((assign_mfma_pruned_reg_kernel<D, NB>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
-                           dim3(64), 0, call.stream, call.x, (long)n, call.img, call.ng, order, hint_sorted, call.bd, call.mask,
-                           call.ngw, reinterpret_cast<long*>(call.ids), call.dist);
-    else
-        AT_LAUNCH((assign_mfma_pruned_kernel<D, NB>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
-                           dim3(64), lds, call.stream, call.x, (long)n, call.img, call.ng, order, hint_sorted, call.bd, call.mask,
-                           call.ngw, reinterpret_cast<long*>(call.ids), call.dist);
+    // d = 64, one or two row tiles: register-staged A operand (no LDS); AT_PRUNE_KERNEL=0 selects the LDS-DMA form
+    // (A/B aid).  Every other shape has the LDS-DMA form only, so the register form is not even instantiated there.
+    if constexpr (D == 64 && NB <= 2) {
+        if (ctx->dbg.prune_kernel != 0) {
+            AT_LAUNCH((assign_mfma_pruned_reg_kernel<D, NB>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
+                               dim3(64), 0, call.stream, call.x, (long)n, call.img, call.ng, order, hint_sorted, call.bd, call.mask,
+                               call.ngw, reinterpret_cast<long*>(call.ids), call.dist);
+            return AT_OK;
+        }
+    }
+    AT_LAUNCH((assign_mfma_pruned_kernel<D, NB>), dim3((unsigned)((n + rows_per_wg - 1) / rows_per_wg)),
+                       dim3(64), lds, call.stream, call.x, (long)n, call.img, call.ng, order, hint_sorted, call.bd, call.mask,
+                       call.ngw, reinterpret_cast<long*>(call.ids), call.dist);
     return AT_OK;
 }
 
