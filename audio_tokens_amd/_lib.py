@@ -129,6 +129,8 @@ SIGNATURES = {
     "at_pq_decode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "at_pq_search_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "at_pq_search_limits": (_i32, [_c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64), _i32, _i64, _i32]),
+    "at_ivf_build_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "at_ivf_search_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "at_rq_encode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "at_rq_decode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "at_rq_beam_step_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -725,6 +725,55 @@ class HipBackend(HostHelpers):
                                                    int(ntotal), int(k)))
         return {"queries_per_block": int(qb.value), "slab_rows": int(slab.value), "queries_per_chunk": int(chunk.value)}
 
+    IVF_TILE_ROWS = 128   # stored rows per tile of the image (csrc/ivf.hip: TILE)
+
+    def ivf_build(self, rows, lists, nlist):
+        """The searchable image of an inverted file (at_ivf_build_f32): rows [ntotal, d] float32 and their list numbers
+        [ntotal] int64 on the device (outside [0, nlist): in no list) -> an opaque record for ivf_search().  The stable
+        order of the rows by list is torch's stable sort; the image is allocated from the host-side bound
+        ntotal // 128 + nlist on its tiles.  Nothing is read back."""
+        rows = self._f32(rows)
+        nlist = int(nlist)
+        assert rows.dim() == 2 and lists.dtype == torch.int64 and lists.shape == (rows.shape[0],)
+        ntotal, d = rows.shape
+        lists = lists.to(self.device).contiguous()
+        unlisted = (lists < 0) | (lists >= nlist)
+        order = torch.sort(torch.where(unlisted, torch.full_like(lists, nlist), lists), stable=True).indices.contiguous()
+        ntiles = ntotal // self.IVF_TILE_ROWS + nlist
+        tile_floats = self.IVF_TILE_ROWS * 64 * ((d + 63) // 64) + 256
+        img = self.empty((ntiles, tile_floats))
+        pos2id = self.empty((ntiles * self.IVF_TILE_ROWS,), torch.int32)
+        first = self.empty((nlist + 1,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_ivf_build_f32(self.ctx.handle, _ptr(rows), _ptr(lists), _ptr(order), ntotal, d, nlist,
+                                                 ntiles, _ptr(img), _ptr(pos2id), _ptr(first), self._stream()))
+        return {"img": img, "pos2id": pos2id, "first": first, "ntiles": ntiles, "ntotal": ntotal, "nlist": nlist, "d": d}
+
+    def ivf_search(self, x, probes, image, k, want_dist=True):
+        """The k nearest stored rows among the probed lists (at_ivf_search_f32): x [n, d], probes [n, nprobe] int64 (list
+        numbers, distinct within a row; -1: no list), image from ivf_build(), 1 <= k <= 32 -> (ids [n, k] int64, dist
+        [n, k] float32 or None), ascending (dis, id), (-1, +inf) in the places left over.  dis is always the expansion
+        form of assign().  Queries whose d is no multiple of 4 are padded with +0, which changes no bit.  k < 1 raises
+        RuntimeError.  Nothing is read back."""
+        k = int(k)
+        if k < 1:
+            raise RuntimeError(f"ivf_search: k must be at least 1, got {k}")
+        x = self._f32(x)
+        assert x.dim() == 2 and x.shape[1] == image["d"], f"ivf_search: expected [n, {image['d']}]"
+        assert probes.dtype == torch.int64 and probes.dim() == 2 and probes.shape[0] == x.shape[0]
+        probes = probes.to(self.device).contiguous()
+        n, d = x.shape
+        if d % 4:
+            x = torch.nn.functional.pad(x, (0, 4 - d % 4)).contiguous()
+        ids = self.empty((n, k), torch.int64)
+        dist = self.empty((n, k), torch.float32) if want_dist else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_ivf_search_f32(self.ctx.handle, _ptr(x), n, x.shape[1], _ptr(probes), probes.shape[1],
+                                                  image["nlist"], _ptr(image["img"]), image["ntiles"],
+                                                  _ptr(image["pos2id"]), _ptr(image["first"]), image["ntotal"], k,
+                                                  _ptr(ids), _ptr(dist), self._stream()))
+        return ids, dist
+
     def rq_encode(self, x, codebooks, want_dist=False, want_residual=False):
         """Greedy residual-quantiser codes (at_rq_encode_f32): x [n, d], codebooks [M, ksub, d] (made float32,
         contiguous, on the device; 1 <= ksub <= 256) -> (codes [n, M] uint8, dist [n, M] float32 or None, residual

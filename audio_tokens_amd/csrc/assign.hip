@@ -50,27 +50,9 @@ __host__ __device__ constexpr int tile_floats(int dp, int na) { return tile_rows
 // (physical) holds logical chunk lc = pc ^ (r & 15); lc = 2q + h holds features 8q + {0,2,4,6} + h.
 // Features >= d and rows >= k are zero; |c|^2 of a row >= k is +inf so it can never win.
 //
-// The 16 bytes of physical slot pc of image row r, from centroid crow (nullptr: a pad row) and the features from f0 on:
-// the swizzle is an involution, so slot pc holds logical slot lc = cs::chunk_slot(r, pc >> 1, pc & 1).
-__device__ __forceinline__ f32x4 image_slot(const float* crow, int d, int f0, int r, int pc) {
-    const int lc = cs::chunk_slot(r, pc >> 1, pc & 1);
-    const int q = lc >> 1, h = lc & 1;
-    f32x4 v;
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const int f = f0 + 8 * q + 2 * u + h;
-        v[u] = (crow && f < d) ? crow[f] : 0.0f;
-    }
-    return v;
-}
-
-// |c|^2 as the ascending fmaf chain; +inf for a pad row
-__device__ __forceinline__ float image_norm(const float* crow, int d) {
-    if (!crow) return __builtin_inff();
-    float nrm = 0.0f;
-    for (int f = 0; f < d; f++) nrm = __builtin_fmaf(crow[f], crow[f], nrm);
-    return nrm;
-}
+// (cs::image_slot / cs::image_norm, chunked_sweep.h: the producers of every image share them.)
+using cs::image_norm;
+using cs::image_slot;
 
 __global__ void __launch_bounds__(WG) prep_centroids_kernel(const float* __restrict__ c, int k, int d,
                                                             int dp, int na, float* __restrict__ img) {

@@ -105,6 +105,7 @@ enum at_ws_slot {
     WS_BLOCK_SCHED,    // at_visit_order_f32: the two halves of the block schedules (exact_plan.h SchedLayout), by call parity
     WS_BLOCK_SCHED_HOOK,   // at_block_sched_install: the caller's schedule
     WS_PQ_SEARCH_LISTS,    // at_pq_search_f32: the k smallest keys of every (query, slab) of a chunk of queries
+    WS_IVF,                // at_ivf_build_f32 / at_ivf_search_f32: list counts and prefix sums; the pair table and the partial lists of a chunk of queries
     WS_NSLOTS
 };
 
@@ -193,6 +194,7 @@ enum at_guard_id {
     AT_GUARD_RQ_BEAM,   // at_rq_beam_step_f32 / at_rq_beam_encode_f32: WS_RQ_BEAM_* (they call at_knn_f32, which takes
                         // AT_GUARD_KNN on the same stream inside: guards do not nest on one another's slots)
     AT_GUARD_PQ_SEARCH, // at_pq_search_f32: WS_PQ_SEARCH_LISTS
+    AT_GUARD_IVF,       // at_ivf_build_f32 / at_ivf_search_f32: WS_IVF
     AT_NGUARDS
 };
 

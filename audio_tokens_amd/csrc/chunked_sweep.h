@@ -106,6 +106,29 @@ __device__ __forceinline__ void load_x_chunk(const float* xrow, int ch, int d, i
     }
 }
 
+// ---- the producer side ---------------------------------------------------------------------------------------------
+// The 16 bytes of physical slot pc of image row r, from centroid crow (nullptr: a pad row) and the features from f0 on:
+// the swizzle is an involution, so slot pc holds logical slot lc = chunk_slot(r, pc >> 1, pc & 1).
+__device__ __forceinline__ f32x4 image_slot(const float* crow, int d, int f0, int r, int pc) {
+    const int lc = chunk_slot(r, pc >> 1, pc & 1);
+    const int q = lc >> 1, h = lc & 1;
+    f32x4 v;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int f = f0 + 8 * q + 2 * u + h;
+        v[u] = (crow && f < d) ? crow[f] : 0.0f;
+    }
+    return v;
+}
+
+// |c|^2 as the ascending fmaf chain; +inf for a pad row
+__device__ __forceinline__ float image_norm(const float* crow, int d) {
+    if (!crow) return __builtin_inff();
+    float nrm = 0.0f;
+    for (int f = 0; f < d; f++) nrm = __builtin_fmaf(crow[f], crow[f], nrm);
+    return nrm;
+}
+
 // ---- the sweep -----------------------------------------------------------------------------------------------------
 // NA accumulators per tile; NCH > 0: d = 64 * NCH and the x chunks stay in registers, NCH = 0: any d % 4 == 0 and the x
 // chunk is re-read per piece; NORMS: the last chunk of a tile drags the tile's norms along into LDS.

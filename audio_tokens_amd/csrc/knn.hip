@@ -8,7 +8,8 @@
 // Fused path (2 <= k <= K_FUSED): the dense sweep over the chunked centroid image (chunked_sweep.h: the layout, the
 // LDS-DMA stream, the x side and the MFMA block; x rows in registers at d = 64, 128, re-read one chunk per stage at any
 // other d that is a multiple of 4), and what this kernel does with a finished tile: a running per-lane top-KL list
-// (KL = the power of two >= k, at least 4) in registers.  A finished accumulator gives each lane 16 candidates; the
+// (KL = the power of two >= k, at least 4) in registers (topk_lanes.h: the list, the pre-test and the merge, shared
+// with ivf.hip).  A finished accumulator gives each lane 16 candidates; the
 // wave first compares their minimum with every lane's KL-th key (one ballot) and then each candidate (one ballot
 // each), so the insert network runs only for candidates that improve some lane.  A lane sees its centroids in
 // ascending index order ((tile, accumulator, register) is ascending in j for a fixed half-wave), so a strict `<` insert that puts a candidate behind its equals keeps the
@@ -26,6 +27,7 @@
 
 #include "at_internal.h"
 #include "chunked_sweep.h"
+#include "topk_lanes.h"
 
 namespace {
 
@@ -40,24 +42,6 @@ __device__ __forceinline__ uint64_t dis_key(float v, unsigned j, int idbits, uin
     unsigned b = __float_as_uint(v);
     if (v == 0.0f) b = 0u;                       // -0 -> +0
     return b < 0x7f800000u ? (((uint64_t)b << idbits) | j) : none;
-}
-
-// insert (c, id) into the ascending list; entries <= c stay in front of it (the lane's ids ascend)
-template <int KL>
-__device__ __forceinline__ void topk_insert(float (&ld)[KL], unsigned (&li)[KL], float c, unsigned id) {
-#pragma unroll
-    for (int s = KL - 1; s > 0; s--) {
-        const bool lt_prev = c < ld[s - 1], lt_here = c < ld[s];
-        ld[s] = lt_prev ? ld[s - 1] : (lt_here ? c : ld[s]);
-        li[s] = lt_prev ? li[s - 1] : (lt_here ? id : li[s]);
-    }
-    const bool lt0 = c < ld[0];
-    ld[0] = lt0 ? c : ld[0];
-    li[0] = lt0 ? id : li[0];
-}
-
-__device__ __forceinline__ bool lex_less(float da, unsigned ia, float db, unsigned ib) {
-    return da < db || (da == db && ia < ib);
 }
 
 // MODE_TOPK: running top-KL per row, written as [n][k];  MODE_KEYS: every (row, centroid) key, [n][kc]
@@ -87,11 +71,7 @@ knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const f
 
     float ld[KL];
     unsigned li[KL];
-#pragma unroll
-    for (int s = 0; s < KL; s++) {
-        ld[s] = __builtin_inff();
-        li[s] = cs::NONE;
-    }
+    tk::clear<KL>(ld, li);
     const long krow = row0 + j;                      // this lane's row (for the keys)
     const uint64_t none = idbits + 31 >= 64 ? ~0ull : ((1ull << (idbits + 31)) - 1ull);
 
@@ -107,12 +87,7 @@ knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const f
             for (int a = 0; a < NA; a++) {
                 const unsigned idbase = (unsigned)cs::acc_base(ct * NA + a, h);
                 float u[16];
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const f32x4 cn = *reinterpret_cast<const f32x4*>(cnorm + a * 32 + 8 * g + 4 * h);
-#pragma unroll
-                    for (int e = 0; e < 4; e++) u[4 * g + e] = __builtin_fmaf(-2.0f, acc[a][4 * g + e], xn + cn[e]);
-                }
+                tk::l2_of_acc16(acc[a], cnorm + a * 32 + 4 * h, xn, u);
                 if constexpr (MODE == MODE_KEYS) {
                     if (krow < n) {
                         uint64_t* kr = keys + krow * (long)kc;
@@ -123,18 +98,7 @@ knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const f
                         }
                     }
                 } else {
-                    // clamp0(u) < kth only if u < kth (kth >= 0): the minimum decides whether anything can enter
-                    float m = __builtin_fminf(u[0], u[1]);
-#pragma unroll
-                    for (int e = 2; e < 16; e += 2) m = __builtin_fminf(__builtin_fminf(m, u[e]), u[e + 1]);
-                    if (__builtin_amdgcn_ballot_w64(m < ld[KL - 1]) != 0) {
-#pragma unroll
-                        for (int e = 0; e < 16; e++) {
-                            const float cv = cs::clamp0(u[e]);
-                            if (__builtin_amdgcn_ballot_w64(cv < ld[KL - 1]) != 0)
-                                topk_insert<KL>(ld, li, cv, idbase + (unsigned)cs::reg_offset(e));
-                        }
-                    }
+                    tk::offer16<KL>(ld, li, u, idbase);
                 }
             }
         }
@@ -156,31 +120,9 @@ knn_mfma_kernel(const float* __restrict__ X, long n, int d, int nchunks, const f
     }
 
     if constexpr (MODE == MODE_TOPK) {
-        // merge the half-waves: min(A[s], B[KL-1-s]) is bitonic and holds the KL smallest; then sort it
         float cd[KL];
         unsigned ci[KL];
-#pragma unroll
-        for (int s = 0; s < KL; s++) {
-            const float od = __shfl_xor(ld[KL - 1 - s], 32);
-            const unsigned oi = (unsigned)__shfl_xor((int)li[KL - 1 - s], 32);
-            const bool take = lex_less(od, oi, ld[s], li[s]);
-            cd[s] = take ? od : ld[s];
-            ci[s] = take ? oi : li[s];
-        }
-#pragma unroll
-        for (int st = KL / 2; st > 0; st /= 2) {
-#pragma unroll
-            for (int s = 0; s < KL; s++) {
-                if (s & st) continue;
-                const bool sw = lex_less(cd[s + st], ci[s + st], cd[s], ci[s]);
-                const float td = cd[s];
-                const unsigned ti = ci[s];
-                cd[s] = sw ? cd[s + st] : cd[s];
-                ci[s] = sw ? ci[s + st] : ci[s];
-                cd[s + st] = sw ? td : cd[s + st];
-                ci[s + st] = sw ? ti : ci[s + st];
-            }
-        }
+        tk::merge_halves<KL>(ld, li, cd, ci);
         if (h == 0 && krow < n) {
             long* io = ids + krow * (long)k;
             float* dout = dist ? dist + krow * (long)k : nullptr;

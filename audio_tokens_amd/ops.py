@@ -22,6 +22,8 @@
         (tools/manual_tester.py: audio -> tokens against a trained vocabulary)
     faiss.ProductQuantizer, faiss.IndexPQ                 ->  ProductQuantizer, IndexPQ
         (not used by the reference: M code bytes per frame, and the search over them)
+    faiss.IndexIVFFlat                                    ->  IndexIVFFlat
+        (not used by the reference: the vocabulary as coarse quantiser, exact search of the probed lists)
     torchaudio.transforms.MFCC, ComputeDeltas             ->  MFCC, ComputeDeltas
         (not used by the reference: the 13 + delta + delta-delta features of HTK / Kaldi-style tokenisers)
 
@@ -51,7 +53,7 @@ __all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "IndexFlatI
            "silhouette_score", "average_precision", "mean_average_precision", "roc_auc", "mean_roc_auc",
            "roc_auc_score", "d_prime", "f1_score", "hamming_loss", "classification_metrics", "load_flac",
            "load_flac_batch", "AudioTokenizer", "ProductQuantizer", "ResidualQuantizer", "MFCC", "ComputeDeltas",
-           "IndexPQ"]
+           "IndexPQ", "IndexIVFFlat"]
 
 
 def _is_host(x) -> bool:
@@ -1217,6 +1219,155 @@ class IndexPQ:
 
     def reconstruct(self, i):
         return self.reconstruct_n(i, 1)[0]
+
+
+class IndexIVFFlat:
+    """faiss.IndexIVFFlat(quantizer, d, nlist) under L2 with train / add / add_core / search(x, k) / reset / ntotal /
+    nprobe / list_sizes: the stored rows are kept grouped by the nearest centroid of `quantizer`, an ops.IndexFlatL2(d),
+    and a query is compared only with the rows of the nprobe lists nearest to it (not used by the reference).  A
+    trained vocabulary is a ready quantiser, and the token of a frame is its list number.
+
+    is_trained is quantizer.ntotal == nlist: a quantiser that already holds nlist rows needs no training; any other
+    non-zero ntotal raises RuntimeError.  train(x) does nothing when trained; otherwise it adds the centroids of
+    Kmeans(d, nlist, niter=10, seed=1234, max_points_per_centroid=256) on x to the quantiser (niter = 10: faiss's
+    level-1 default).
+
+    add(x) appends rows with the ids ntotal, ntotal + 1, ...; the list of a row is quantizer.assign(x), the exact
+    search the tokeniser makes (a row with a NaN or Inf in it gets no list).  add_core(x, precomputed_idx) takes the caller's int64 list numbers as they are (tokens
+    already computed); values outside [-1, nlist) raise.  A row whose list is -1 (a NaN row, a row no centroid is
+    listable for) counts in ntotal and sits in no list, as in faiss; add() with check_finite=True (the default) raises
+    RuntimeError in faiss's words for such a row before anything is appended, check_finite=False skips that one host
+    read.  Adding before training raises.  The searchable image is built at the first search after an add and cached;
+    the raw rows are kept beside it (DESIGN.md section 6o says what that costs).  reset() drops the stored rows and
+    keeps the quantiser.
+
+    search(x, k) returns (D, I), [n, k] float32 / int64: numpy for host input, device tensors (on the caller's current
+    stream) for device input.  The contract, the library's own:
+      * the probed lists of query i are the ids in row i of backend.knn(x, centroids, min(nprobe, nlist)) -- at_knn_f32
+        itself, its direct form for n < 20 included; a -1 slot is no list; only the set matters;
+      * dis(i, r) between query i and stored row r is ALWAYS the expansion form of at_assign_f32, whatever n is: ip,
+        |x|^2, |r|^2 ascending fmaf chains, (xn + rn) - 2*ip in one fma, the clamp v < 0 ? 0 : v (a NaN stays a NaN);
+      * row i lists the k smallest (dis, id) in lexicographic order over the stored rows of its probed lists with
+        dis < +inf; the slots left over hold I = -1, D = +inf (IndexFlatL2.search's conventions);
+      * so with nprobe >= nlist, n >= 20 and no unlisted stored row the result equals
+        IndexFlatL2(d).add(stored).search(x, k) bit for bit.
+    nprobe (default 1): values above nlist act as nlist, values below 1 raise at search.  k < 1 raises RuntimeError,
+    k > 32 NotImplementedError (the per-lane list of the kernel, as in IndexFlatL2's fused path; a larger k is a
+    follow-up).  No remove_ids, add_with_ids, reconstruct or inner-product metric."""
+
+    MAX_K = 32
+
+    def __init__(self, quantizer, d, nlist, backend=None):
+        self.d, self.nlist = int(d), int(nlist)
+        if self.nlist < 1:
+            raise ValueError(f"IndexIVFFlat: nlist = {nlist} (at least one list)")
+        if not isinstance(quantizer, IndexFlatL2) or quantizer.d != self.d:
+            raise ValueError(f"IndexIVFFlat: the quantizer must be an ops.IndexFlatL2({self.d})")
+        self.quantizer = quantizer
+        self.backend = backend or quantizer.backend
+        for need in ("knn", "ivf_build", "ivf_search"):
+            if not hasattr(self.backend, need):
+                raise NotImplementedError(f"IndexIVFFlat needs a backend with {need}()")
+        self.nprobe = 1
+        self._x = None        # [ntotal, d] float32, the raw rows
+        self._lists = None    # [ntotal] int64
+        self._image = None    # backend.ivf_build's record, built lazily
+        _ = self.is_trained
+
+    @property
+    def is_trained(self) -> bool:
+        have = self.quantizer.ntotal
+        if have not in (0, self.nlist):
+            raise RuntimeError(f"IndexIVFFlat: the quantizer holds {have} rows, the index has nlist = {self.nlist} lists")
+        return have == self.nlist
+
+    @property
+    def ntotal(self) -> int:
+        return 0 if self._x is None else int(self._x.shape[0])
+
+    @property
+    def list_sizes(self):
+        """int64 numpy [nlist]: the rows in every list (rows in no list are in none)."""
+        sizes = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.backend.device)
+        if self._lists is not None:
+            at = torch.where(self._lists < 0, torch.full_like(self._lists, self.nlist), self._lists)
+            sizes.scatter_add_(0, at, torch.ones_like(at))
+        return self.backend.to_host(sizes[:self.nlist].contiguous())
+
+    def train(self, x) -> None:
+        if self.is_trained:
+            return
+        km = Kmeans(self.d, self.nlist, niter=10, seed=1234, max_points_per_centroid=256, backend=self.backend)
+        km.train(self._rows(x, "IndexIVFFlat.train"))
+        self.quantizer.add(km.centroids_device)
+
+    def reset(self) -> None:
+        self._x = self._lists = self._image = None
+
+    def _rows(self, x, what):
+        x = self.backend._f32(x)
+        assert x.dim() == 2 and x.shape[1] == self.d, f"{what}: expected [n, {self.d}], got {tuple(x.shape)}"
+        return x
+
+    def _append(self, x, lists) -> None:
+        self._x = x.clone() if self._x is None else torch.cat([self._x, x], 0)
+        self._lists = lists.clone() if self._lists is None else torch.cat([self._lists, lists], 0)
+        self._image = None
+
+    def add(self, x, check_finite=True) -> None:
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFFlat.add: the index is not trained (call train(), or hand it a full quantizer)")
+        x = self._rows(x, "IndexIVFFlat.add")
+        if x.shape[0] == 0:
+            return
+        lists, _ = self.quantizer.assign(x, want_dist=False)
+        # at_assign_f32 clamps with fmaxf, which turns the NaN distances of a row with a NaN or Inf in it into 0 and
+        # names centroid 0; the oracle, at_knn_f32 and this index list no centroid for such a row
+        lists = torch.where(torch.isfinite(x).all(1), lists, torch.full_like(lists, -1))
+        if check_finite and bool((lists < 0).any().item()):
+            raise RuntimeError("Error: 'std::isfinite(x_in[i])' failed: input contains NaN's or Inf's")
+        self._append(x, lists)
+
+    def add_core(self, x, precomputed_idx) -> None:
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFFlat.add_core: the index is not trained (call train(), or hand it a full quantizer)")
+        x = self._rows(x, "IndexIVFFlat.add_core")
+        if isinstance(precomputed_idx, np.ndarray):
+            precomputed_idx = torch.from_numpy(np.ascontiguousarray(precomputed_idx))
+        lists = torch.as_tensor(precomputed_idx)
+        if lists.dtype != torch.int64 or lists.dim() != 1 or lists.shape[0] != x.shape[0]:
+            raise ValueError(f"IndexIVFFlat.add_core: expected int64 list numbers [{x.shape[0]}]")
+        if x.shape[0] == 0:
+            return
+        lists = lists.to(self.backend.device).contiguous()
+        lo, hi = int(lists.min().item()), int(lists.max().item())
+        if lo < -1 or hi >= self.nlist:
+            raise RuntimeError(f"IndexIVFFlat.add_core: list numbers {lo} .. {hi} outside -1 .. {self.nlist - 1}")
+        self._append(x, lists)
+
+    def search(self, x, k=1):
+        k = int(k)
+        if k < 1:
+            raise RuntimeError(f"IndexIVFFlat.search: k must be at least 1, got {k}")
+        if k > self.MAX_K:
+            raise NotImplementedError(f"IndexIVFFlat.search: k = {k} (at most {self.MAX_K} neighbours are implemented)")
+        nprobe = int(self.nprobe)
+        if nprobe < 1:
+            raise RuntimeError(f"IndexIVFFlat.search: nprobe must be at least 1, got {nprobe}")
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFFlat.search: the index is not trained (call train(), or hand it a full quantizer)")
+        be = self.backend
+        host = _is_host(x)
+        x = self._rows(x, "IndexIVFFlat.search")
+        if self._x is None or x.shape[0] == 0:
+            D = torch.full((x.shape[0], k), float("inf"), device=be.device)
+            I = torch.full((x.shape[0], k), -1, dtype=torch.int64, device=be.device)
+        else:
+            if self._image is None:
+                self._image = be.ivf_build(self._x, self._lists, self.nlist)
+            probes, _ = be.knn(x, self.quantizer._c, min(nprobe, self.nlist), want_dist=False)
+            I, D = be.ivf_search(x, probes, self._image, k)
+        return (be.to_host(D), be.to_host(I)) if host else (D, I)
 
 
 class ResidualQuantizer:

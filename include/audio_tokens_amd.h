@@ -20,6 +20,7 @@
  *   faiss.IndexFlatIP(d).search(x, 1), Kmeans(spherical=True) (likewise)   at_assign_ip_f32, at_renorm_rows_f32
  *   faiss.ProductQuantizer(d, M, 8).compute_codes(x) / .decode(codes) (likewise)  at_pq_encode_f32, at_pq_decode_f32
  *   faiss.IndexPQ(d, M, 8).search(x, k) over stored codes (likewise; the library's own contract)  at_pq_search_f32
+ *   faiss.IndexIVFFlat(quantizer, d, nlist).search(x, k) (likewise; the library's own contract)  at_ivf_build_f32, at_ivf_search_f32
  *   greedy residual quantiser (RVQ, beam 1; the library's own contract)    at_rq_encode_f32, at_rq_decode_f32
  *   beam-search residual quantiser (beam 1 .. 32; the library's own contract)  at_rq_beam_step_f32, at_rq_beam_encode_f32
  *   torchaudio.transforms.MFCC / ComputeDeltas on log-mel rows (likewise)  at_mfcc_f32, at_deltas_f32,
@@ -579,6 +580,47 @@ int at_pq_decode_f32(at_ctx* ctx, const uint8_t* codes, int64_t n, int d, int M,
  * for it. */
 int at_pq_search_f32(at_ctx* ctx, const float* x, int64_t n, int d, int M, int ksub, const float* codebooks,
                      const uint8_t* codes, int64_t ntotal, int k, int64_t* ids, float* dist_or_null, void* stream);
+
+/* Inverted lists over exact fp32 rows (faiss IndexIVFFlat under L2; ops.IndexIVFFlat; the contract is the library's
+ * own).  The stored rows are kept grouped by list number, and a query is compared only with the rows of the lists it
+ * probes.
+ *   Probed lists: the entries of row i of probes ([n][nprobe] int64) that lie in [0, nlist); anything else (-1) is no
+ *     list.  The entries of a row must be distinct -- ops passes row i of at_knn_f32(x, centroids, min(nprobe, nlist)),
+ *     its direct form for n < 20 included; only the SET matters.
+ *   Distance: dis(i, r) between query i and stored row r is ALWAYS the expansion form of at_assign_f32, whatever n is:
+ *     ip, |x|^2, |r|^2 ascending fmaf chains, (xn + rn) - 2*ip in one fma, the clamp v < 0 ? 0 : v, which leaves a NaN a
+ *     NaN.  Features padded with +0 (queries up to a multiple of 4, both sides up to the chunk of 64) change no bit.
+ *   Result: row i lists the k smallest (dis, id) in lexicographic order over the stored rows of its probed lists with
+ *     dis < +inf; the places left over hold ids = -1, dist = +inf.
+ *   Consequence: with every list probed, n >= 20 and no stored row outside the lists, the result is at_knn_f32's over
+ *     the stored rows, bit for bit.
+ *
+ * at_ivf_build_f32 makes the searchable image of rows [ntotal][d] (any d >= 1) whose list numbers are lists [ntotal]
+ * int64 (outside [0, nlist): in no list, never found).  order [ntotal] int64 names the rows sorted by list number,
+ * STABLY, so that ids ascend inside a list, with the rows of no list last (a position whose row is not of the list the
+ * position belongs to becomes a pad: a wrong order loses rows, it cannot address out of range).  Outputs, all sized by
+ * the caller from ntiles >= ntotal / 128 + nlist (a host-side bound: nothing is read back):
+ *   img: float [ntiles][cs::tile_floats(4, ceil(d / 64))], csrc/chunked_sweep.h's chunked image, every list padded to
+ *     whole tiles of 128 rows, a pad row all +0 with norm +inf; 16-byte aligned;
+ *   pos2id: int32 [ntiles * 128], the id of the row at a position of the image, -1 for a pad;
+ *   first: int32 [nlist + 1], the first tile of every list; first[nlist] = tiles in use.
+ * 0 <= ntotal < 2^31, ntiles * 128 < 2^31, 1 <= nlist <= 2^24.  Three launches; the list counts live in the context.
+ *
+ * at_ivf_search_f32: x [n][d] fp32 with d % 4 == 0, 16-byte aligned -- d is the row width of the build rounded up to a
+ * multiple of 4, the features behind the build's d being +0; img / ntiles / pos2id / first / ntotal / nlist as built;
+ * 1 <= k <= 32 (the per-lane list of at_knn_f32's fused path; there is no path behind it), nprobe >= 1; ids: int64
+ * [n][k]; dist_or_null: float [n][k].  n == 0 is a no-op that touches no pointer.  Anything else is AT_E_INVALID, before
+ * any launch.  Per chunk of queries (their partial lists, 8 bytes per (query, probe, place), within 256 MiB of context
+ * workspace): a counting sort of the (query, probe) pairs by list, the scan -- a workgroup of four waves takes one
+ * (list, block of up to 128 probing queries), gathers the queries as the MFMA B operand, streams the list's tiles
+ * through LDS by LDS-DMA and keeps at_knn_f32's running per-lane top-k; d = 64 and 128 keep the query in registers,
+ * any other d re-reads it per chunk -- and the merge of a query's nprobe partial lists.  No host synchronisation, no
+ * device-to-host copy; a call on another stream than the context's previous at_ivf_* call waits for it. */
+int at_ivf_build_f32(at_ctx* ctx, const float* rows, const int64_t* lists, const int64_t* order, int64_t ntotal, int d,
+                     int nlist, int ntiles, float* img, int32_t* pos2id, int32_t* first, void* stream);
+int at_ivf_search_f32(at_ctx* ctx, const float* x, int64_t n, int d, const int64_t* probes, int nprobe, int nlist,
+                      const float* img, int ntiles, const int32_t* pos2id, const int32_t* first, int64_t ntotal, int k,
+                      int64_t* ids, float* dist_or_null, void* stream);
 
 /* Residual quantiser (RVQ), greedy encoder: beam width 1, M dependent stages.  r_0 = x; for m = 0 .. M-1 in order,
  * (codes[i][m], dist[i][m]) is at_assign_f32's answer for the rows r_m against codebooks[m] ([ksub][d]), bit for bit:
