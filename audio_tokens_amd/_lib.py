@@ -130,6 +130,10 @@ SIGNATURES = {
     "at_pq_search_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "at_pq_search_limits": (_i32, [_c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64), _i32, _i64, _i32]),
     "at_ivf_build_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "at_ivfpq_build": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "at_ivfpq_search_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _i32,
+                                   _vp, _vp, _vp]),
+    "at_ivfpq_search_limits": (_i32, [_c.POINTER(_i32), _c.POINTER(_i32), _c.POINTER(_i64), _i32, _i32, _i32]),
     "at_ivf_search_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "at_rq_encode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "at_rq_decode_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -774,6 +774,73 @@ class HipBackend(HostHelpers):
                                                   _ptr(ids), _ptr(dist), self._stream()))
         return ids, dist
 
+    IVFPQ_GROUP_ROWS = 16   # rows a list of the grouped codes is padded to (csrc/ivfpq.hip: GROUP)
+
+    def ivfpq_build(self, codes, lists, nlist):
+        """The searchable image of PQ codes behind inverted lists (at_ivfpq_build): codes [ntotal, M] uint8 and their list
+        numbers [ntotal] int64 on the device (outside [0, nlist): in no list) -> an opaque record for ivfpq_search().
+        The stable order of the rows by list is torch's stable sort; everything is allocated from the host-side bound
+        ntotal // 16 + nlist on the groups of 16 rows.  Nothing is read back."""
+        nlist = int(nlist)
+        if isinstance(codes, np.ndarray):
+            codes = torch.from_numpy(np.ascontiguousarray(codes))
+        assert codes.dtype == torch.uint8 and codes.dim() == 2, "ivfpq_build: codes must be uint8 [ntotal, M]"
+        assert lists.dtype == torch.int64 and lists.shape == (codes.shape[0],)
+        codes = codes.to(self.device).contiguous()
+        ntotal, M = codes.shape
+        lists = lists.to(self.device).contiguous()
+        unlisted = (lists < 0) | (lists >= nlist)
+        order = torch.sort(torch.where(unlisted, torch.full_like(lists, nlist), lists), stable=True).indices.contiguous()
+        ngroups = ntotal // self.IVFPQ_GROUP_ROWS + nlist
+        grouped = self.empty((ngroups * self.IVFPQ_GROUP_ROWS, M), torch.uint8)
+        pos2id = self.empty((ngroups * self.IVFPQ_GROUP_ROWS,), torch.int32)
+        first = self.empty((nlist + 1,), torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_ivfpq_build(self.ctx.handle, _ptr(codes), _ptr(lists), _ptr(order), ntotal, M, nlist,
+                                               ngroups, _ptr(grouped), _ptr(pos2id), _ptr(first), self._stream()))
+        return {"codes": grouped, "pos2id": pos2id, "first": first, "ngroups": ngroups, "ntotal": ntotal, "nlist": nlist,
+                "M": M}
+
+    def ivfpq_search(self, x, probes, centroids, codebooks, image, k, want_dist=True):
+        """The k nearest stored codes among the probed lists (at_ivfpq_search_f32): x [n, d], probes [n, nprobe] int64
+        (list numbers, distinct within a row; -1: no list), centroids [nlist, d] (the query of a (query, list) pair is
+        x - centroid, one fp32 subtraction per feature) or None (the query is x itself), codebooks [M, ksub, d / M],
+        image from ivfpq_build(), 1 <= k <= 128 -> (ids [n, k] int64, dist [n, k] float32 or None), ascending
+        (dis, id), (-1, +inf) in the places left over.  dis is pq_search()'s: direct-form tables, added in ascending m.
+        k < 1 raises RuntimeError.  Nothing is read back."""
+        k = int(k)
+        if k < 1:
+            raise RuntimeError(f"ivfpq_search: k must be at least 1, got {k}")
+        x, cb = self._f32(x), self._f32(codebooks)
+        assert x.dim() == 2 and cb.dim() == 3, "ivfpq_search: x must be [n, d] and codebooks [M, ksub, dsub]"
+        assert probes.dtype == torch.int64 and probes.dim() == 2 and probes.shape[0] == x.shape[0]
+        probes = probes.to(self.device).contiguous()
+        n, d = x.shape
+        M, ksub, dsub = cb.shape
+        if M * dsub != d or M != image["M"]:
+            raise ValueError(f"ivfpq_search: codebooks {tuple(cb.shape)} do not cut rows of {d} features into {image['M']} codes")
+        cent = None
+        if centroids is not None:
+            cent = self._f32(centroids)
+            assert cent.shape == (image["nlist"], d), f"ivfpq_search: centroids must be [{image['nlist']}, {d}]"
+        ids = self.empty((n, k), torch.int64)
+        dist = self.empty((n, k), torch.float32) if want_dist else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.at_ivfpq_search_f32(self.ctx.handle, _ptr(x), n, d, _ptr(probes), probes.shape[1],
+                                                    image["nlist"], _ptr(cent), M, ksub, _ptr(cb), _ptr(image["codes"]),
+                                                    image["ngroups"], _ptr(image["pos2id"]), _ptr(image["first"]),
+                                                    image["ntotal"], k, _ptr(ids), _ptr(dist), self._stream()))
+        return ids, dist
+
+    @staticmethod
+    def ivfpq_search_limits(M, nprobe, k) -> dict:
+        """include/at_debug.h, at_ivfpq_search_limits: (query, probe) pairs per workgroup, rows per group of the image
+        and queries per chunk of an ivfpq_search() call of that shape (for the tests that sit on those seams)."""
+        qb, group, chunk = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+        _lib.check(_lib.load().at_ivfpq_search_limits(ctypes.byref(qb), ctypes.byref(group), ctypes.byref(chunk), int(M),
+                                                      int(nprobe), int(k)))
+        return {"pairs_per_block": int(qb.value), "rows_per_group": int(group.value), "queries_per_chunk": int(chunk.value)}
+
     def rq_encode(self, x, codebooks, want_dist=False, want_residual=False):
         """Greedy residual-quantiser codes (at_rq_encode_f32): x [n, d], codebooks [M, ksub, d] (made float32,
         contiguous, on the device; 1 <= ksub <= 256) -> (codes [n, M] uint8, dist [n, M] float32 or None, residual

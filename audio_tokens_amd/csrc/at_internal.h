@@ -106,6 +106,7 @@ enum at_ws_slot {
     WS_BLOCK_SCHED_HOOK,   // at_block_sched_install: the caller's schedule
     WS_PQ_SEARCH_LISTS,    // at_pq_search_f32: the k smallest keys of every (query, slab) of a chunk of queries
     WS_IVF,                // at_ivf_build_f32 / at_ivf_search_f32: list counts and prefix sums; the pair table and the partial lists of a chunk of queries
+    WS_IVFPQ,              // at_ivfpq_build / at_ivfpq_search_f32: list counts and prefix sums; the pair table and the partial lists of a chunk of queries
     WS_NSLOTS
 };
 
@@ -195,6 +196,7 @@ enum at_guard_id {
                         // AT_GUARD_KNN on the same stream inside: guards do not nest on one another's slots)
     AT_GUARD_PQ_SEARCH, // at_pq_search_f32: WS_PQ_SEARCH_LISTS
     AT_GUARD_IVF,       // at_ivf_build_f32 / at_ivf_search_f32: WS_IVF
+    AT_GUARD_IVFPQ,     // at_ivfpq_build / at_ivfpq_search_f32: WS_IVFPQ
     AT_NGUARDS
 };
 

@@ -30,6 +30,7 @@
 // a formality).
 #include "at_internal.h"
 #include "chunked_sweep.h"
+#include "pair_inversion.h"
 #include "topk_lanes.h"
 
 namespace {
@@ -44,64 +45,11 @@ constexpr size_t BUDGET_BYTES = (size_t)256 << 20;   // the partial lists of one
 constexpr int64_t MAX_PAIRS = (int64_t)1 << 30;      // (query, probe) pairs of one chunk: pair indices are ints
 constexpr uint64_t KEY_NONE = ~(uint64_t)0;
 
-// cnt[l] += 1 for every entry l of v in [0, nlist); anything else (-1: no list) is skipped
-__global__ void __launch_bounds__(WG)
-ivf_count_kernel(const long* __restrict__ v, long m, int nlist, int* __restrict__ cnt) {
-    const long t = (long)blockIdx.x * WG + threadIdx.x;
-    if (t >= m) return;
-    const long l = v[t];
-    if (l >= 0 && l < nlist) atomicAdd(cnt + l, 1);
-}
-
-// start[l] = sum of cnt[0 .. l), units[l] = sum of ceil(cnt / per) over [0 .. l), l = 0 .. nlist; one workgroup, thread
-// t owns the lists [t * seg, (t + 1) * seg)
-__global__ void __launch_bounds__(WG)
-ivf_offsets_kernel(const int* __restrict__ cnt, int nlist, int per, int* __restrict__ start, int* __restrict__ units) {
-    __shared__ int sa[WG], sb[WG];
-    const int t = threadIdx.x;
-    const int seg = (nlist + WG - 1) / WG;
-    const int l0 = t * seg < nlist ? t * seg : nlist, l1 = l0 + seg < nlist ? l0 + seg : nlist;
-    int a = 0, b = 0;
-    for (int l = l0; l < l1; l++) {
-        a += cnt[l];
-        b += (cnt[l] + per - 1) / per;
-    }
-    sa[t] = a;
-    sb[t] = b;
-    __syncthreads();
-    if (t == 0) {
-        int ra = 0, rb = 0;
-        for (int i = 0; i < WG; i++) {
-            const int ca = sa[i], cb = sb[i];
-            sa[i] = ra;
-            sb[i] = rb;
-            ra += ca;
-            rb += cb;
-        }
-        start[nlist] = ra;
-        units[nlist] = rb;
-    }
-    __syncthreads();
-    a = sa[t];
-    b = sb[t];
-    for (int l = l0; l < l1; l++) {
-        start[l] = a;
-        units[l] = b;
-        a += cnt[l];
-        b += (cnt[l] + per - 1) / per;
-    }
-}
-
-// the l in [0, nlist) with tab[l] <= b < tab[l + 1]; the caller has checked b < tab[nlist] (tab[0] = 0, tab ascends)
-__device__ __forceinline__ int list_of_unit(const int* __restrict__ tab, int nlist, int b) {
-    int lo = 0, hi = nlist;   // tab[lo] <= b < tab[hi] throughout
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tab[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
+// the counting sort of the pairs and list_of_unit: pair_inversion.h (shared with ivfpq.hip)
+using pinv::ivf_count_kernel;
+using pinv::ivf_offsets_kernel;
+using pinv::ivf_scatter_kernel;
+using pinv::list_of_unit;
 
 // one workgroup per tile of the image
 __global__ void __launch_bounds__(WG)
@@ -143,22 +91,6 @@ ivf_image_kernel(const float* __restrict__ rows, const long* __restrict__ lists,
     for (int r = threadIdx.x; r < cs::CN_PAD; r += WG) {
         const long id = r < TILE ? src[r] : -1;
         out[(size_t)cs::piece_floats(NA) * nchunks + r] = cs::image_norm(id >= 0 ? rows + (size_t)id * d : nullptr, d);
-    }
-}
-
-// pair p with a list: into its list's stretch of pairtab; without one: its k places of the partial lists are empty
-__global__ void __launch_bounds__(WG)
-ivf_scatter_kernel(const long* __restrict__ probes, int ptotal, int nlist, const int* __restrict__ pair_start,
-                   int* __restrict__ cursor, int* __restrict__ pairtab, uint64_t* __restrict__ partial, int k) {
-    const int p = blockIdx.x * WG + threadIdx.x;
-    if (p >= ptotal) return;
-    const long l = probes[p];
-    if (l >= 0 && l < nlist) {
-        // cursor[l] counts the same pairs ivf_count_kernel counted: slot < pair_start[l + 1] <= ptotal
-        const int slot = pair_start[l] + atomicAdd(cursor + l, 1);
-        if (slot >= 0 && slot < ptotal) pairtab[slot] = p;
-    } else {
-        for (int s = 0; s < k; s++) partial[(size_t)p * k + s] = KEY_NONE;
     }
 }
 

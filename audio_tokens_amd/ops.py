@@ -24,6 +24,8 @@
         (not used by the reference: M code bytes per frame, and the search over them)
     faiss.IndexIVFFlat                                    ->  IndexIVFFlat
         (not used by the reference: the vocabulary as coarse quantiser, exact search of the probed lists)
+    faiss.IndexIVFPQ                                      ->  IndexIVFPQ
+        (not used by the reference: PQ codes behind the vocabulary's lists, searched without being decoded)
     torchaudio.transforms.MFCC, ComputeDeltas             ->  MFCC, ComputeDeltas
         (not used by the reference: the 13 + delta + delta-delta features of HTK / Kaldi-style tokenisers)
 
@@ -53,7 +55,7 @@ __all__ = ["LogMelSpectrogram", "Resample", "Kmeans", "IndexFlatL2", "IndexFlatI
            "silhouette_score", "average_precision", "mean_average_precision", "roc_auc", "mean_roc_auc",
            "roc_auc_score", "d_prime", "f1_score", "hamming_loss", "classification_metrics", "load_flac",
            "load_flac_batch", "AudioTokenizer", "ProductQuantizer", "ResidualQuantizer", "MFCC", "ComputeDeltas",
-           "IndexPQ", "IndexIVFFlat"]
+           "IndexPQ", "IndexIVFFlat", "IndexIVFPQ"]
 
 
 def _is_host(x) -> bool:
@@ -1368,6 +1370,214 @@ class IndexIVFFlat:
             probes, _ = be.knn(x, self.quantizer._c, min(nprobe, self.nlist), want_dist=False)
             I, D = be.ivf_search(x, probes, self._image, k)
         return (be.to_host(D), be.to_host(I)) if host else (D, I)
+
+
+class IndexIVFPQ:
+    """faiss.IndexIVFPQ(quantizer, d, nlist, M, nbits=8) under L2 with train / add / add_core / search(x, k) /
+    reconstruct / reset / ntotal / nprobe / list_sizes / codes: the stored rows are kept as the M code bytes of `pq`, an
+    ops.ProductQuantizer(d, M, ...) built from the constructor's arguments (same errors for d % M and nbits), grouped by
+    the nearest centroid of `quantizer`, an ops.IndexFlatL2(d), and a query meets only the codes of the nprobe lists
+    nearest to it (not used by the reference).  The contract is the library's own, in the manner of IndexPQ and
+    IndexIVFFlat: recalled, not verified against faiss output.
+
+    is_trained is quantizer.ntotal == nlist (any other non-zero ntotal raises RuntimeError) and pq.is_trained.  train(x)
+    first trains an empty quantiser as IndexIVFFlat.train does, then trains pq on x - c[assign(x)] (a device gather and
+    one fp32 subtraction), or on x itself when by_residual is False.
+
+    add(x) appends rows with the ids ntotal, ntotal + 1, ...; the list of a row is quantizer.assign(x), -1 for a row
+    with a NaN or Inf in it, which counts in ntotal, sits in no list and is never found; with check_finite=True (the
+    default) such a row raises RuntimeError in faiss's words before anything is appended.  add_core(x, precomputed_idx)
+    takes the caller's int64 list numbers in [-1, nlist).  Row r of list l >= 0 stores pq.compute_codes(x[r] - c[l])
+    (by_residual, one fp32 subtraction per feature) or pq.compute_codes(x[r]); a row of list -1 is encoded from a
+    zero vector.  `codes` is the uint8 device tensor [ntotal, M] in id order, kept beside the grouped image (built
+    at the first search after an add, and cached).  reset() keeps the quantiser and the codebooks.
+    reconstruct_n(i0, n) / reconstruct(i) give pq.decode(codes), plus c[list] in one fp32 addition when by_residual,
+    and NaN rows for list -1 (numpy).
+
+    search(x, k) returns (D, I), [n, k] float32 / int64: numpy for host input, device tensors (on the caller's current
+    stream) for device input:
+      * the probed lists of query i are the ids in row i of backend.knn(x, centroids, min(nprobe, nlist)); a -1 slot
+        is no list;
+      * for query i and probed list l the query vector is q = x[i] - c[l] (one fp32 subtraction per feature) when
+        by_residual, x[i] itself otherwise; the table is T[m, j] = sum_f (q[m*dsub + f] - codebook[m, j, f])^2 in
+        IndexPQ's direct form (one subtraction, an ascending fmaf chain from +0), and a row r of list l has
+        dis(i, r) = T[0, code[r, 0]] + T[1, code[r, 1]] + ..., one fp32 addition per step in ascending m.  The
+        expansion form appears nowhere; faiss's precomputed-table decomposition of the residual distance is a
+        different arithmetic and is not implemented;
+      * row i lists the k smallest (dis, id) in lexicographic order over the stored rows of its probed lists with
+        dis < +inf (NaN never is); the slots left over hold I = -1, D = +inf; a non-finite query lists nothing;
+      * so with by_residual=False, nprobe >= nlist and no unlisted row the result equals IndexPQ.search(x, k) over
+        the same codebooks and codes bit for bit, for every n.
+    nprobe (default 1): values above nlist act as nlist, values below 1 raise at search.  k < 1 raises RuntimeError;
+    k > 128, M > 64 and nlist > 2^24 raise NotImplementedError, and so does a backend without ivfpq_build() /
+    ivfpq_search().  No inner-product metric, remove_ids, add_with_ids, polysemous codes or nbits != 8."""
+
+    MAX_M, MAX_K, MAX_NLIST = 64, 128, 1 << 24
+
+    def __init__(self, quantizer, d, nlist, M, nbits=8, by_residual=True, niter=25, seed=1234,
+                 max_points_per_centroid=256, verbose=False, backend=None):
+        self.d, self.nlist = int(d), int(nlist)
+        if self.nlist < 1:
+            raise ValueError(f"IndexIVFPQ: nlist = {nlist} (at least one list)")
+        if self.nlist > self.MAX_NLIST:
+            raise NotImplementedError(f"IndexIVFPQ: nlist = {nlist} (at most {self.MAX_NLIST} lists are implemented)")
+        if not isinstance(quantizer, IndexFlatL2) or quantizer.d != self.d:
+            raise ValueError(f"IndexIVFPQ: the quantizer must be an ops.IndexFlatL2({self.d})")
+        self.quantizer = quantizer
+        self.backend = backend or quantizer.backend
+        self.pq = ProductQuantizer(d, M, nbits=nbits, niter=niter, seed=seed,
+                                   max_points_per_centroid=max_points_per_centroid, verbose=verbose, backend=self.backend)
+        if self.pq.M > self.MAX_M:
+            raise NotImplementedError(f"IndexIVFPQ: M = {self.pq.M} (at most {self.MAX_M} sub-quantisers are implemented)")
+        for need in ("knn", "ivfpq_build", "ivfpq_search"):
+            if not hasattr(self.backend, need):
+                raise NotImplementedError(f"IndexIVFPQ needs a backend with {need}()")
+        self.M, self.by_residual = self.pq.M, bool(by_residual)
+        self.nprobe = 1
+        self._codes = None    # [ntotal, M] uint8, in id order
+        self._lists = None    # [ntotal] int64
+        self._image = None    # backend.ivfpq_build's record, built lazily
+        _ = self.is_trained
+
+    @property
+    def is_trained(self) -> bool:
+        have = self.quantizer.ntotal
+        if have not in (0, self.nlist):
+            raise RuntimeError(f"IndexIVFPQ: the quantizer holds {have} rows, the index has nlist = {self.nlist} lists")
+        return have == self.nlist and self.pq.is_trained
+
+    @property
+    def ntotal(self) -> int:
+        return 0 if self._codes is None else int(self._codes.shape[0])
+
+    @property
+    def codes(self):
+        """The stored codes in id order, a uint8 device tensor [ntotal, M]."""
+        if self._codes is None:
+            return self.backend.empty((0, self.M), torch.uint8)
+        return self._codes
+
+    @property
+    def list_sizes(self):
+        """int64 numpy [nlist]: the rows in every list (rows in no list are in none)."""
+        sizes = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.backend.device)
+        if self._lists is not None:
+            at = torch.where(self._lists < 0, torch.full_like(self._lists, self.nlist), self._lists)
+            sizes.scatter_add_(0, at, torch.ones_like(at))
+        return self.backend.to_host(sizes[:self.nlist].contiguous())
+
+    def _rows(self, x, what):
+        x = self.backend._f32(x)
+        assert x.dim() == 2 and x.shape[1] == self.d, f"{what}: expected [n, {self.d}], got {tuple(x.shape)}"
+        return x
+
+    def _encoder_input(self, x, lists):
+        """What the encoder sees of the rows x with the list numbers `lists`: x - c[list] (by_residual) or x, and a zero
+        vector for a row of list -1."""
+        out = x
+        if self.by_residual:
+            out = x - self.quantizer._c[lists.clamp(min=0)]
+        return torch.where((lists < 0)[:, None], torch.zeros_like(out), out).contiguous()
+
+    def train(self, x) -> None:
+        x = self._rows(x, "IndexIVFPQ.train")
+        if self.quantizer.ntotal != self.nlist:
+            _ = self.is_trained   # (raises for a quantiser of another size)
+            km = Kmeans(self.d, self.nlist, niter=10, seed=1234, max_points_per_centroid=256, backend=self.backend)
+            km.train(x)
+            self.quantizer.add(km.centroids_device)
+        if self.by_residual:
+            lists, _ = self.quantizer.assign(x, want_dist=False)
+            x = (x - self.quantizer._c[lists.clamp(min=0)]).contiguous()
+        self.pq.train(x)
+
+    def reset(self) -> None:
+        self._codes = self._lists = self._image = None
+
+    def _append(self, x, lists, check_finite) -> None:
+        codes = self.pq.compute_codes(self._encoder_input(x, lists), check_finite=check_finite)
+        if isinstance(codes, np.ndarray):   # (a backend whose device is the host answers with numpy)
+            codes = torch.from_numpy(np.ascontiguousarray(codes))
+        codes = codes.to(self.backend.device).contiguous()
+        self._codes = codes.clone() if self._codes is None else torch.cat([self._codes, codes], 0)
+        self._lists = lists.clone() if self._lists is None else torch.cat([self._lists, lists], 0)
+        self._image = None
+
+    def add(self, x, check_finite=True) -> None:
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFPQ.add: the index is not trained (call train(), or hand it a full quantizer and pq.set_centroids())")
+        x = self._rows(x, "IndexIVFPQ.add")
+        if x.shape[0] == 0:
+            return
+        lists, _ = self.quantizer.assign(x, want_dist=False)
+        # (IndexIVFFlat.add: the assignment names centroid 0 for a row with a NaN or Inf in it; such a row gets no list)
+        lists = torch.where(torch.isfinite(x).all(1), lists, torch.full_like(lists, -1))
+        if check_finite and bool((lists < 0).any().item()):
+            raise RuntimeError("Error: 'std::isfinite(x_in[i])' failed: input contains NaN's or Inf's")
+        self._append(x, lists, check_finite)
+
+    def add_core(self, x, precomputed_idx) -> None:
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFPQ.add_core: the index is not trained (call train(), or hand it a full quantizer and pq.set_centroids())")
+        x = self._rows(x, "IndexIVFPQ.add_core")
+        if isinstance(precomputed_idx, np.ndarray):
+            precomputed_idx = torch.from_numpy(np.ascontiguousarray(precomputed_idx))
+        lists = torch.as_tensor(precomputed_idx)
+        if lists.dtype != torch.int64 or lists.dim() != 1 or lists.shape[0] != x.shape[0]:
+            raise ValueError(f"IndexIVFPQ.add_core: expected int64 list numbers [{x.shape[0]}]")
+        if x.shape[0] == 0:
+            return
+        lists = lists.to(self.backend.device).contiguous()
+        lo, hi = int(lists.min().item()), int(lists.max().item())
+        if lo < -1 or hi >= self.nlist:
+            raise RuntimeError(f"IndexIVFPQ.add_core: list numbers {lo} .. {hi} outside -1 .. {self.nlist - 1}")
+        self._append(x, lists, False)
+
+    def search(self, x, k=1):
+        k = int(k)
+        if k < 1:
+            raise RuntimeError(f"IndexIVFPQ.search: k must be at least 1, got {k}")
+        if k > self.MAX_K:
+            raise NotImplementedError(f"IndexIVFPQ.search: k = {k} (at most {self.MAX_K} neighbours are implemented)")
+        nprobe = int(self.nprobe)
+        if nprobe < 1:
+            raise RuntimeError(f"IndexIVFPQ.search: nprobe must be at least 1, got {nprobe}")
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFPQ.search: the index is not trained (call train(), or hand it a full quantizer and pq.set_centroids())")
+        be = self.backend
+        host = _is_host(x)
+        x = self._rows(x, "IndexIVFPQ.search")
+        if self._codes is None or x.shape[0] == 0:
+            D = torch.full((x.shape[0], k), float("inf"), device=be.device)
+            I = torch.full((x.shape[0], k), -1, dtype=torch.int64, device=be.device)
+        else:
+            if self._image is None:
+                self._image = be.ivfpq_build(self._codes, self._lists, self.nlist)
+            probes, _ = be.knn(x, self.quantizer._c, min(nprobe, self.nlist), want_dist=False)
+            I, D = be.ivfpq_search(x, probes, self.quantizer._c if self.by_residual else None, self.pq.centroids_device,
+                                   self._image, k)
+        return (be.to_host(D), be.to_host(I)) if host else (D, I)
+
+    def reconstruct_n(self, i0=0, n=-1):
+        """float32 numpy [n, d]: the decoded rows i0 .. i0 + n - 1 (n = -1: to the end), NaN for a row of list -1."""
+        i0, n = int(i0), int(n)
+        if n < 0:
+            n = self.ntotal - i0
+        if i0 < 0 or n < 0 or i0 + n > self.ntotal:
+            raise RuntimeError(f"IndexIVFPQ.reconstruct_n: rows {i0} .. {i0 + n} of {self.ntotal}")
+        if n == 0:
+            return np.zeros((0, self.d), np.float32)
+        out = self.pq.decode(self._codes[i0:i0 + n])
+        if isinstance(out, np.ndarray):
+            out = torch.from_numpy(out)
+        lists = self._lists[i0:i0 + n]
+        if self.by_residual:
+            out = out + self.quantizer._c[lists.clamp(min=0)]
+        out = torch.where((lists < 0)[:, None], torch.full_like(out, float("nan")), out)
+        return self.backend.to_host(out.contiguous())
+
+    def reconstruct(self, i):
+        return self.reconstruct_n(i, 1)[0]
 
 
 class ResidualQuantizer:

@@ -54,6 +54,11 @@
  *                                 places: queries per workgroup (4 up to M = 32, 2 above), database rows per slab, and
  *                                 the queries whose lists fill the workspace budget -- a call with more takes them in
  *                                 chunks of that many (NULL skips a field).  No device work.
+ *   at_ivfpq_search_limits        the seams of at_ivfpq_search_f32 for a call with M sub-spaces, nprobe probes per query
+ *                                 and k places: (query, probe) pairs per workgroup (4 up to M = 32, 2 above), the rows a
+ *                                 list of the image is padded to, and the queries whose partial lists fill the workspace
+ *                                 budget -- a call with more takes them in chunks of that many (NULL skips a field).  No
+ *                                 device work.
  */
 #ifndef AUDIO_TOKENS_AMD_DEBUG_H
 #define AUDIO_TOKENS_AMD_DEBUG_H
@@ -84,6 +89,7 @@ int at_block_sched_last(at_ctx* ctx, int* path, int* tiles, int64_t* blocks);
 int at_block_sched_limits(int64_t* one_tile_max_rows, int64_t* two_tile_max_rows);
 int at_waccum_limits(int* short_batch, int* short_batch_wide, int* long_list, int* ring_chunk);
 int at_pq_search_limits(int* queries_per_block, int* slab_rows, int64_t* queries_per_chunk, int M, int64_t ntotal, int k);
+int at_ivfpq_search_limits(int* pairs_per_block, int* rows_per_group, int64_t* queries_per_chunk, int M, int nprobe, int k);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@
  *   faiss.ProductQuantizer(d, M, 8).compute_codes(x) / .decode(codes) (likewise)  at_pq_encode_f32, at_pq_decode_f32
  *   faiss.IndexPQ(d, M, 8).search(x, k) over stored codes (likewise; the library's own contract)  at_pq_search_f32
  *   faiss.IndexIVFFlat(quantizer, d, nlist).search(x, k) (likewise; the library's own contract)  at_ivf_build_f32, at_ivf_search_f32
+ *   faiss.IndexIVFPQ(quantizer, d, nlist, M, 8).search(x, k) (likewise; the library's own contract)  at_ivfpq_build, at_ivfpq_search_f32
  *   greedy residual quantiser (RVQ, beam 1; the library's own contract)    at_rq_encode_f32, at_rq_decode_f32
  *   beam-search residual quantiser (beam 1 .. 32; the library's own contract)  at_rq_beam_step_f32, at_rq_beam_encode_f32
  *   torchaudio.transforms.MFCC / ComputeDeltas on log-mel rows (likewise)  at_mfcc_f32, at_deltas_f32,
@@ -621,6 +622,54 @@ int at_ivf_build_f32(at_ctx* ctx, const float* rows, const int64_t* lists, const
 int at_ivf_search_f32(at_ctx* ctx, const float* x, int64_t n, int d, const int64_t* probes, int nprobe, int nlist,
                       const float* img, int ntiles, const int32_t* pos2id, const int32_t* first, int64_t ntotal, int k,
                       int64_t* ids, float* dist_or_null, void* stream);
+
+/* Product-quantiser codes behind inverted lists (faiss IndexIVFPQ under L2; ops.IndexIVFPQ; the contract is the
+ * library's own -- recalled, not verified against faiss output).  The stored rows are kept as M code bytes grouped by
+ * list number, and a query meets only the codes of the lists it probes.
+ *   Probed lists: as for at_ivf_search_f32 -- the entries of row i of probes ([n][nprobe] int64) in [0, nlist), distinct
+ *     within a row; anything else (-1) is no list.
+ *   Distance: for query i and probed list l the query vector is q = x[i] - centroids[l], one fp32 subtraction per
+ *     feature (by_residual), or x[i] itself when centroids_or_null is NULL.  The table is T[m][j] = sum_f (q[m * dsub + f]
+ *     - codebooks[m][j][f])^2 in at_pq_search_f32's direct form (df one subtraction, acc = fmaf(df, df, acc) from +0 over
+ *     ascending f) and dis(i, r) = T[0][code[r][0]] + T[1][code[r][1]] + ..., one fp32 addition per step in ascending m,
+ *     for the rows r of list l.  The expansion form appears nowhere; faiss's precomputed-table decomposition of the
+ *     residual distance is a different arithmetic and is not implemented.
+ *   Result: row i holds the k smallest (dis, id) in lexicographic order over the stored rows of its probed lists with
+ *     dis < +inf (a NaN never is); the places left over hold ids = -1, dist = +inf.  No flag word: a non-finite query
+ *     lists nothing.  A stored code >= ksub (possible only with ksub < 256) makes that row unlisted and is never used as
+ *     an index.
+ *   Consequence: without centroids, with every list probed and no stored row outside the lists, the result is
+ *     at_pq_search_f32's over the same codebooks and codes, bit for bit, for every n.
+ *
+ * at_ivfpq_build groups codes (uint8 [ntotal][M], 1 <= M <= 64) by the list numbers lists [ntotal] int64 (outside
+ * [0, nlist): in no list, never found).  order [ntotal] int64 names the rows sorted by list number, STABLY, so that ids
+ * ascend inside a list, with the rows of no list last (a position whose row is not of the list the position belongs to
+ * becomes a pad: a wrong order loses rows, it cannot address out of range).  Outputs, all sized by the caller from
+ * ngroups >= ntotal / 16 + nlist (a host-side bound: nothing is read back):
+ *   grouped: uint8 [ngroups * 16][M], every list padded to whole groups of 16 rows (a list then starts at a multiple
+ *     of 16 bytes for any M), pads all 0;
+ *   pos2id: int32 [ngroups * 16], the id of the row at a position, -1 for a pad;
+ *   first: int32 [nlist + 1], the first group of every list; first[nlist] = groups in use.
+ * 0 <= ntotal < 2^31, ngroups * 16 < 2^31, 1 <= nlist <= 2^24.  Three launches; the list counts live in the context.
+ *
+ * at_ivfpq_search_f32: x [n][d] fp32 (any 4-byte alignment), codebooks [M][ksub][d / M], centroids_or_null [nlist][d];
+ * grouped / ngroups / pos2id / first / ntotal / nlist as built (grouped is read with 16-, 8- or 4-byte loads where M and
+ * its address allow); d % M == 0, 1 <= M <= 64, 1 <= ksub <= 256, 1 <= k <= 128, nprobe >= 1; ids: int64 [n][k];
+ * dist_or_null: float [n][k].  n == 0 is a no-op that touches no pointer.  Anything else is AT_E_INVALID, before any
+ * launch: there is no path behind M <= 64 (the tables of a workgroup's pairs stay in LDS) or k <= 128 (so do its
+ * candidates).  Per chunk of queries (their partial lists, 8 bytes per (query, probe, place), within 256 MiB of context
+ * workspace; at most 2^30 pairs): at_ivf_search_f32's counting sort of the (query, probe) pairs by list, in blocks of 4
+ * pairs (2 for M > 32); the scan -- one workgroup per (list, block of pairs) builds the tables of its pairs in LDS and
+ * walks the list's rows with at_pq_search_f32's look-up loop and candidate buffer; a list of any length is walked by its
+ * own workgroups alone, long lists are not split --; and at_pq_search_f32's streaming merge over a query's nprobe * k
+ * keys.  No host synchronisation, no device-to-host copy; a call on another stream than the context's previous
+ * at_ivfpq_* call waits for it. */
+int at_ivfpq_build(at_ctx* ctx, const uint8_t* codes, const int64_t* lists, const int64_t* order, int64_t ntotal, int M,
+                   int nlist, int ngroups, uint8_t* grouped, int32_t* pos2id, int32_t* first, void* stream);
+int at_ivfpq_search_f32(at_ctx* ctx, const float* x, int64_t n, int d, const int64_t* probes, int nprobe, int nlist,
+                        const float* centroids_or_null, int M, int ksub, const float* codebooks, const uint8_t* grouped,
+                        int ngroups, const int32_t* pos2id, const int32_t* first, int64_t ntotal, int k, int64_t* ids,
+                        float* dist_or_null, void* stream);
 
 /* Residual quantiser (RVQ), greedy encoder: beam width 1, M dependent stages.  r_0 = x; for m = 0 .. M-1 in order,
  * (codes[i][m], dist[i][m]) is at_assign_f32's answer for the rows r_m against codebooks[m] ([ksub][d]), bit for bit:
